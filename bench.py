@@ -15,6 +15,9 @@ fraud-process hand-off); then the epoch's device counters + latency histogram ar
 all-reduced over RCCL on a side stream (X2/X3), overlapped with the next step.
 
     python bench.py                      # 1 GPU, defaults finish in well under a minute
+    python bench.py --full               # + bandwidth probes, unloaded latency, precision vs the fp32
+                                         #   oracle, encoder cost, f32-row rate (null in a plain run)
+    python bench.py --dump-outputs DIR   # + the last timed step's outputs as DIR/<name>.npy
     python bench.py --gpus 8             # spawns 8 local ranks (torch.distributed.run child)
     torchrun --nproc-per-node 8 bench.py --gpus 8 --steps 100 --warmup 10   # same, driver-style
 
@@ -120,6 +123,16 @@ def parse_args(argv=None):
                          "injection, launch serialisation, ...); the line is then labelled diagnostic and "
                          "must not be quoted as a headline")
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the H2D / host-DRAM bandwidth "
+                         "probes, the unloaded latency probe, the precision run against the fp32 oracle, "
+                         "the host row-encoder cost and the f32-row throughput run (each still has its own "
+                         "switch above).  Without it those fields of the JSON line are null")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0: after the timed steps, write what the last timed step handed its caller "
+                         "as DIR/<name>.npy (see _dump_outputs): the fraud-routed records of the hand-off "
+                         "and the route of every log row.  The last step is sized to replay every log row, "
+                         "so the arrays depend on the arguments only, not on the machine's speed")
     return ap.parse_args(argv)
 
 
@@ -395,6 +408,48 @@ def _f32_wire_rate(args, model, dev, exec_mode, seconds: float = 0.5):
     return n / dt
 
 
+DUMP_MAX_ROUTE_ROWS = 1 << 23        # route.npy: 32 MB of float32 at the most
+DUMP_MAX_FLAGGED = 1 << 20           # five flagged_*.npy columns: 28 MB at the most
+
+
+def _dump_outputs(dirpath, records, parts, rows_per_part: int, seed: int) -> None:
+    """``--dump-outputs DIR``: what the last timed step handed its caller, as .npy arrays.
+
+    The timed path returns per-row results through the router hand-off: the fraud-routed
+    records (the kernels' own proba_1 and the row's id, customer, amount and partition); a row
+    that is not handed off was routed standard.  ``records`` are the hand-offs from the start
+    of the last timed step on.  That step replays every log row (main() sizes it so), so one
+    record per distinct transaction id -- the lowest proba where a row came by twice -- is the
+    same set in every run with the same arguments:
+
+    - ``flagged_tx_id`` / ``flagged_partition`` / ``flagged_customer`` (float64, exact) and
+      ``flagged_proba`` / ``flagged_amount`` (float32), ordered by transaction id; at most
+      DUMP_MAX_FLAGGED records (the lowest ids);
+    - ``route`` (float32): 1.0 where the log row was fraud-routed, else 0.0, this rank's
+      partitions in ascending order, rows in log order; of more than DUMP_MAX_ROUTE_ROWS rows
+      a seeded sample, its row numbers in ``route_index`` (float64)."""
+    d = Path(dirpath)
+    d.mkdir(parents=True, exist_ok=True)
+    rec = np.concatenate(records) if records else np.zeros(0, dtype=[
+        ("tx_id", "<u8"), ("customer", "<u4"), ("proba", "<f4"), ("amount", "<f4"), ("partition", "<u4")])
+    rec = rec[np.lexsort((rec["proba"], rec["tx_id"]))]
+    rec = rec[np.unique(rec["tx_id"], return_index=True)[1]]
+    parts = sorted(parts)
+    slot = {p: i for i, p in enumerate(parts)}
+    route = np.zeros(len(parts) * rows_per_part, np.float32)
+    row = (rec["tx_id"] & np.uint64((1 << 40) - 1)).astype(np.int64)
+    route[np.array([slot[int(p)] for p in rec["partition"]], np.int64) * rows_per_part + row] = 1.0
+    if route.size > DUMP_MAX_ROUTE_ROWS:
+        idx = np.sort(np.random.default_rng(seed).choice(route.size, DUMP_MAX_ROUTE_ROWS, replace=False))
+        np.save(d / "route_index.npy", idx.astype(np.float64))
+        route = route[idx]
+    np.save(d / "route.npy", route)
+    rec = rec[:DUMP_MAX_FLAGGED]
+    for name, dt in (("tx_id", np.float64), ("partition", np.float64), ("customer", np.float64),
+                     ("proba", np.float32), ("amount", np.float32)):
+        np.save(d / f"flagged_{name}.npy", rec[name].astype(dt))
+
+
 def main(argv=None):
     args = parse_args(argv)
     from ccfd_demo_summit_amd.utils import benchenv
@@ -478,7 +533,7 @@ def main(argv=None):
     # ---- per-rank H2D ceiling probe, all ranks at once (attributes any scaling loss to the
     # host side: DRAM / PCIe root contention shows up as a lower per-rank GB/s at N > 1)
     h2d_gbps = None
-    if args.probe_ms > 0 and args.input_mode == "zerocopy":
+    if args.full and args.probe_ms > 0 and args.input_mode == "zerocopy":
         wd_state["last_collective"] = "barrier:h2d_probe"
         barrier(ctx)
         h2d_gbps = _h2d_probe(lib, args.probe_ms)
@@ -487,7 +542,7 @@ def main(argv=None):
     # phase 1: every rank at once (each sees its share of its node); phase 2: the lowest rank
     # of each (host, node) alone with the node's threads while the node's other ranks wait
     host_bw = host_threads = node_bw_lead = node_threads = None
-    if args.host_probe_s > 0:
+    if args.full and args.host_probe_s > 0:
         wd_state["last_collective"] = "barrier:host_probe"
         barrier(ctx)
         host_bw, host_threads = _host_read_probe(lib, args.host_probe_s)
@@ -530,6 +585,7 @@ def main(argv=None):
     reducer = CounterReducer(ctx, dev, priority=0)
     epochs = EpochPipeline(eng, reducer)
     flagged_total = 0
+    last_step_records = None     # --dump-outputs: the hand-offs from the start of the last timed step on
     x2_s = [0.0]
     nstep = [0]
     bps = [args.batches_per_step]
@@ -556,6 +612,8 @@ def main(argv=None):
         nonlocal flagged_total
         with handoff_mu:
             flagged_total += len(records)
+            if last_step_records is not None:
+                last_step_records.append(records)
 
     # the router's collector: a thread drains the flagged ring while this thread keeps the
     # micro-batches coming (as the streaming service's native serving thread + collector do);
@@ -594,6 +652,11 @@ def main(argv=None):
     per_batch_s = all_max(ctx, (time.perf_counter() - tc) / (cal_steps * bps[0]))
     need = int(np.ceil(args.min_timed_s * 1.05 / max(1, args.steps) / max(per_batch_s, 1e-9)))
     bps[0] = max(args.batches_per_step, need)
+    if args.dump_outputs:
+        # a step replays every row of this rank's logs at least once (twice over: coalesced
+        # launches may visit the partitions unevenly), so what the last step hands off is a
+        # function of the logs alone, whatever step size the calibration arrived at
+        bps[0] = max(bps[0], 2 * len(my_parts) * (rows_per_part // args.batch))
     step_s_est = bps[0] * per_batch_s
     x2_every[0] = args.x2_every or max(1, int(round(args.x2_period_ms / 1e3 / max(step_s_est, 1e-9))))
     eng.pump(0, drain=True)
@@ -618,6 +681,8 @@ def main(argv=None):
     t0 = time.perf_counter()
     drainer.start()
     for k in range(args.steps):
+        if k == args.steps - 1 and args.dump_outputs and ctx.rank == 0:
+            last_step_records = []
         step(drain=(k == args.steps - 1))
         watchdog.beat(f"timed step {k}")
     drainer.stop()               # every fraud record of the timed batches handed off in the region
@@ -637,6 +702,8 @@ def main(argv=None):
     rows_local[0] += st_final.rows
     handoff(eng.drain_flagged())
     handoff_stalls = st_final.flag_full_events - full0
+    if last_step_records is not None:
+        _dump_outputs(args.dump_outputs, last_step_records, my_parts, rows_per_part, args.seed)
     if args.trace and ctx.rank == 0:
         from ccfd_demo_summit_amd.utils.tracing import dump_batch_trace
         dump_batch_trace(eng.read_trace(), args.trace, name=f"engine rank 0 ({args.model})")
@@ -680,7 +747,7 @@ def main(argv=None):
 
     # unloaded latency probe (not timed): one micro-batch at a time, depth 1
     p50_unloaded = None
-    if not args.no_unloaded_probe:
+    if args.full and not args.no_unloaded_probe:
         probe = StreamEngine(dm, batch=args.batch, depth=1, streams=1, input_mode=args.input_mode,
                              output_mode=args.output_mode, threshold=args.threshold, device=dev.index,
                              exec_mode=exec_mode)
@@ -694,9 +761,9 @@ def main(argv=None):
     for log in logs:
         log.free()
 
-    # precision evidence + f32-row throughput (rank 0, after the timed region)
+    # --full: precision evidence + f32-row throughput (rank 0, after the timed region)
     precision = f32_rate = encode = None
-    if ctx.rank == 0:
+    if ctx.rank == 0 and args.full:
         if args.precision_rows > 0:
             precision = _precision(model, dm, args, dev, exec_mode)
         if args.encode_probe_rows > 0:

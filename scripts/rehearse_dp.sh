@@ -20,6 +20,6 @@ grep -m3 "topology check failed" "$O/refuse.log" || { tail -20 "$O/refuse.log"; 
 # config 2: `python bench.py --gpus N` spawns the N ranks (launch/local_ranks.py); --rehearsal
 # makes the parent hand its children the gloo / shared-GPU env
 unset CCFD_DIST_BACKEND CCFD_DEVICE_MODULO
-timeout -k 10 300 python bench.py --gpus "$N" --rehearsal --out "$O/bench_dp${N}_rehearsal.json" "$@" \
+timeout -k 10 300 python bench.py --gpus "$N" --rehearsal --full --out "$O/bench_dp${N}_rehearsal.json" "$@" \
   > "$O/rehearsal.log" 2>&1 || { tail -40 "$O/rehearsal.log"; exit 1; }
 python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print('rehearsal dp%d' % d['n_gpus'], '%.4g tx/s' % d['value'], 'p50', d['p50_latency_us'], 'timed', d['timed_region_s'], [ (r['rank'], r['tx_s'], r['h2d_zerocopy_GBps']) for r in d['per_rank']])" "$O/bench_dp${N}_rehearsal.json"

@@ -82,6 +82,40 @@ def test_single_rank_mismatch_refused():
     assert problems == [] and idents[0]["pci"] == "p"
 
 
+def test_dump_outputs_depend_on_the_records_not_their_arrival(tmp_path):
+    """bench.py --dump-outputs: the arrays are the same however often and in whatever order
+    the last step's hand-off delivered a log row's record."""
+    import numpy as np
+    sys.path.insert(0, str(ROOT))
+    import bench
+    from ccfd_demo_summit_amd.ops._lib import FLAGGED_DTYPE
+    rows = 1000
+    rec = np.zeros(6, dtype=np.dtype(FLAGGED_DTYPE))
+    rec["partition"] = [3, 3, 1, 1, 3, 1]
+    rec["tx_id"] = np.array([5, 999, 0, 17, 42, 18], np.uint64) + (rec["partition"].astype(np.uint64) << np.uint64(40))
+    rec["proba"] = [0.9, 0.6, 0.7, 0.8, 0.55, 0.5]
+    rec["amount"] = [1.5, 2.5, 3.5, 4.5, 5.5, 6.5]
+    rec["customer"] = [7, 8, 9, 10, 11, 12]
+    rng = np.random.default_rng(0)
+    a = [rec[rng.permutation(6)], rec[:3]]                      # the first three rows came by twice
+    b = [rec[::-1][:2], rec[::-1][2:]]
+    for name, chunks in (("a", a), ("b", b)):
+        bench._dump_outputs(tmp_path / name, chunks, [3, 1], rows, seed=0)
+    out = {n: {p.stem: np.load(p) for p in (tmp_path / n).glob("*.npy")} for n in "ab"}
+    assert set(out["a"]) == {"route", "flagged_tx_id", "flagged_partition", "flagged_customer",
+                             "flagged_proba", "flagged_amount"}
+    for k, v in out["a"].items():
+        assert v.dtype == (np.float32 if k in ("route", "flagged_proba", "flagged_amount") else np.float64)
+        np.testing.assert_array_equal(v, out["b"][k])
+    # partitions ascending (1, then 3), rows in log order
+    np.testing.assert_array_equal(np.flatnonzero(out["a"]["route"]), [0, 17, 18, 1005, 1042, 1999])
+    np.testing.assert_array_equal(out["a"]["flagged_partition"], [1, 1, 1, 3, 3, 3])
+    np.testing.assert_array_equal(out["a"]["flagged_proba"], np.float32([0.7, 0.8, 0.5, 0.9, 0.55, 0.6]))
+    np.testing.assert_array_equal(out["a"]["flagged_tx_id"] % (1 << 40), [0, 17, 18, 5, 42, 999])
+    assert bench._dump_outputs(tmp_path / "empty", [], [0], 8, seed=0) is None
+    assert np.load(tmp_path / "empty" / "route.npy").sum() == 0
+
+
 def test_e2e_refuses_isolated_stacks_at_n_gt_1():
     """bench/e2e.py builds a private broker + KIE per rank: at WORLD_SIZE > 1 that is N isolated
     stacks, not config 5 -- refused without --allow-isolated, and labelled when allowed."""

@@ -28,7 +28,11 @@ def test_api_doc_gpu_blocks_run(gpu, tmp_path, monkeypatch):
     b = _blocks()
     ns = {}
     exec(b[0].replace('"mlp.safetensors"', repr(str(tmp_path / "m.safetensors"))), ns)
-    exec(b[1], ns)
+    try:
+        exec(b[1], ns)
+    finally:
+        if ns.get("eng") is not None:
+            ns["eng"].close()      # a block that raised must not leave its persistent kernel resident
     assert ns["st"].rows == 100 * 4096 and ns["proba"].shape == (1000,)
     exec(b[2], ns)
     assert ns["dm"].row_format == "g20" and ns["mine"]
