@@ -12,6 +12,8 @@ compared with the two ceilings of the kernel on MI355X:
 
     python bench/kernel_sol.py [--out profiles/r1/kernel_sol.json]
     python bench/kernel_sol.py --cases mlp:w64 --sizes 16777216 --flags 48   # ablation
+    python bench/kernel_sol.py --cases forest:f32,gbdt:f32 --sizes 1048576,16777216            # general trees:
+    python bench/kernel_sol.py --cases forest:f32 --forest random --forest-lds-multiple 4      # LDS / L2 node table
 """
 from __future__ import annotations
 
@@ -68,6 +70,12 @@ def main():
                          "instead of HBM: one launch per size, no engine")
     ap.add_argument("--gbdt-trees", type=int, default=100)
     ap.add_argument("--gbdt-depth", type=int, default=6)
+    ap.add_argument("--forest", default="oblivious", choices=["oblivious", "random"],
+                    help="forest:f32 case: the --gbdt-trees x --gbdt-depth ensemble expanded into general trees "
+                         "(node table in LDS when it fits), or random unbalanced depth-12 trees")
+    ap.add_argument("--forest-lds-multiple", type=float, default=4.0,
+                    help="--forest random: node table of about this many times the kernel's LDS budget "
+                         "(> 1: walked from global memory / L2)")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import torch
@@ -89,8 +97,19 @@ def main():
         xw = torch.from_numpy(encode_wire(X)).to(dev).repeat(reps, 1)[:nmax].contiguous()
     results = []
     for kind, wire in cases:
-        m = build_model(kind, seed=0, X_ref=X[:100_000], calibrate_rate=0.01, gbdt_trees=args.gbdt_trees,
-                        gbdt_depth=args.gbdt_depth)
+        if kind == "forest":
+            from ccfd_demo_summit_amd.models import TreeEnsemble
+            from ccfd_demo_summit_amd.models.forest import LDS_NODE_BYTES, NODE_BYTES
+            if args.forest == "oblivious":
+                m = TreeEnsemble.from_oblivious(build_model("gbdt", seed=0, X_ref=X[:100_000], calibrate_rate=0.01,
+                                                            gbdt_trees=args.gbdt_trees, gbdt_depth=args.gbdt_depth))
+            else:       # 64 random depth-12 trees at p_leaf 0.295 are about one LDS budget of nodes
+                m = TreeEnsemble.random_init(max(1, round(64 * args.forest_lds_multiple)), 12, 0.295, 0, X[:20_000])
+            forest_info = {"forest": args.forest, "trees": m.n_trees, "max_depth": m.depth, "nodes": m.n_nodes,
+                           "node_table": "lds" if m.n_nodes * NODE_BYTES <= LDS_NODE_BYTES else "global"}
+        else:
+            m = build_model(kind, seed=0, X_ref=X[:100_000], calibrate_rate=0.01, gbdt_trees=args.gbdt_trees,
+                            gbdt_depth=args.gbdt_depth)
         dm = DeviceModel(m, dev, wire=(wire == "w64"), bins=wire if wire in ("g32", "g20") else None)
         if wire in ("g32", "g20"):
             xg = torch.from_numpy(dm.bins.encode(X)).to(dev).repeat(reps, 1)[:nmax].contiguous()
@@ -123,6 +142,8 @@ def main():
                  "rows_in": "host-zerocopy" if args.host else "hbm",
                  "us_per_launch": round(us, 2), "G_rows_per_s": round(rows_s / 1e9, 3), "GBps": round(gbps, 1),
                  "frac_hbm_roofline": round(gbps / HBM_GBPS_MEASURED, 3)}
+            if kind == "forest":
+                r.update(forest_info)
             if kind == "mlp":
                 tf = rows_s * MLP_FLOP_PER_ROW / 1e12
                 r["mfma_TFLOPs"] = round(tf, 1)

@@ -312,7 +312,8 @@ class StreamEngine:
                  device: Optional[int] = None, flag_capacity: int = 1 << 20, exec_mode: str = "launch",
                  persist_grid: int = 0, coalesce: int = 1, rules=None, persist_items: str = "auto"):
         """exec_mode: "launch" = one fused kernel launch per micro-batch; "persistent" = one
-        long-running kernel fed through a descriptor ring (MLP/LR, zero-copy outputs).
+        long-running kernel fed through a descriptor ring (MLP/LR, zero-copy outputs; general
+        trees -- kind "forest" -- have a launch-mode kernel only).
         persist_items (persistent MLP on W64 rows): "claimed" = 512-row items claimed by 64
         workgroups (the throughput point: 8.7e8 tx/s at 12 batches in flight); "pipelined" =
         static 128-row items over 128 workgroups with the next item's rows fetched while the
@@ -476,9 +477,10 @@ class StreamEngine:
 
     def swap_model(self, dm: DeviceModel) -> None:
         """Hot swap (runtime X1): in-flight micro-batches finish on the old weights, later ones
-        use ``dm``.  The new model must have the same kernel kind, row format and GBDT shape."""
+        use ``dm``.  The new model must have the same kernel kind, row format and GBDT shape
+        (a forest may change its tree and node counts: its kernel takes them from the blob)."""
         if dm.kind != self.dm.kind or dm.row_format != self.row_format or \
-                (dm.trees, dm.depth) != (self.dm.trees, self.dm.depth):
+                (dm.kind != "forest" and (dm.trees, dm.depth) != (self.dm.trees, self.dm.depth)):
             raise ValueError("hot swap needs a model of the same kind / wire format / tree shape")
         if self.row_format in BIN_FORMATS and not same_bins(dm.bins, self.bins):
             raise ValueError("G32 hot swap: pack the new ensemble against the live bin table "

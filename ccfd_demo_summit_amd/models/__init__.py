@@ -1,4 +1,5 @@
-"""Model families: logistic regression, 3-layer MLP, oblivious GBDT, user-task model.
+"""Model families: logistic regression, 3-layer MLP, oblivious GBDT, general tree ensembles
+(random forests / boosted trees), user-task model.
 
 Versioned weight files are safetensors (``kind`` + ``version`` in the metadata) --
 the replacement for the reference's "model baked into the image, imagePullPolicy
@@ -11,13 +12,14 @@ from typing import Union
 import numpy as np
 
 from .common import Normalizer, bf16_round, sigmoid
+from .forest import TreeEnsemble
 from .gbdt import ObliviousGBDT
 from .lr import LogisticModel
 from .mlp import MLPModel
 from .usertask import UserTaskModel
 
-AnyModel = Union[LogisticModel, MLPModel, ObliviousGBDT]
-KINDS = {"lr": LogisticModel, "mlp": MLPModel, "gbdt": ObliviousGBDT}
+AnyModel = Union[LogisticModel, MLPModel, ObliviousGBDT, TreeEnsemble]
+KINDS = {"lr": LogisticModel, "mlp": MLPModel, "gbdt": ObliviousGBDT, "forest": TreeEnsemble}
 
 
 def build_model(kind: str, seed: int = 0, X_ref=None, calibrate_rate=None, threshold: float = 0.5,
@@ -56,5 +58,5 @@ def load_model(path: str) -> AnyModel:
     return KINDS[kind].from_state_dict(st)
 
 
-__all__ = ["Normalizer", "LogisticModel", "MLPModel", "ObliviousGBDT", "UserTaskModel",
+__all__ = ["Normalizer", "LogisticModel", "MLPModel", "ObliviousGBDT", "TreeEnsemble", "UserTaskModel",
            "build_model", "save_model", "load_model", "KINDS", "bf16_round", "sigmoid"]

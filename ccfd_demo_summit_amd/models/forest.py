@@ -1,0 +1,261 @@
+"""General (non-oblivious) binary decision-tree ensembles: random forests, extra trees,
+scikit-learn / XGBoost boosted trees (importers: models/sklearn_import.py,
+models/xgboost_import.py; device kernel: csrc/kernels/score_forest.hip).
+
+Every inner node has its own test: a row goes RIGHT iff ``x[feat] > thr`` as a float32
+compare -- the predicate of the oblivious kernels, so NaN goes left (transactions are dense
+floats; missing-value routing is out of scope).  Nodes live ensemble-wide in one array and
+the two children of a node are adjacent: left = ``child``, right = ``child + 1``.  A leaf
+carries one float32 value.  Each tree has a root node index and a depth (longest
+root-to-leaf path; a single-leaf tree has depth 0).
+
+``z = base + sum_t leaf_t(x)``; ``proba = sigmoid(z)`` for ``link == "sigmoid"`` (boosted
+trees), ``clip(z, 0, 1)`` for ``link == "identity"`` (forests that average class fractions:
+their leaves are pre-scaled by 1/T).  Features are RAW (trees are scale invariant).
+
+Blob for the kernel (16-B aligned sections):
+  [0,64)  header 'FRS1', flags (bit 0 = sigmoid link), T (i32), max_depth (i32), base (f32),
+          n_nodes (i32)
+  tree    i32  [T][2]       {root node index, depth}
+  node    [n_nodes] x 8 B   {u32 w, f32 v}
+            w bits 0..4  = feature, bit 5 = leaf flag, bits 8..31 = index of the left child
+            v            = threshold of an inner node, value of a leaf
+          a leaf's child field is its own index, so one step of the walk is
+          ``next = leaf ? cur : child + (x[feat] > v)`` and a finished row stays put.
+"""
+from __future__ import annotations
+
+import struct
+from dataclasses import dataclass
+from typing import Optional
+
+import numpy as np
+
+from ..contracts.transaction import N_FEATURES
+from .common import HEADER_BYTES, header, pad16, sigmoid
+from .gbdt import ObliviousGBDT
+
+MAX_DEPTH = 64
+MAX_NODES = 1 << 24              # the blob's child field is 24 bits
+# Node-table bytes the kernel keeps in LDS (csrc/kernels/score_forest.hip kNodeLdsBytes);
+# larger tables are walked from global memory (L2).
+LDS_NODE_BYTES = 144 * 1024
+NODE_BYTES = 8
+LINKS = ("sigmoid", "identity")
+
+
+@dataclass
+class TreeEnsemble:
+    feat: np.ndarray      # int32 [n_nodes]   feature of an inner node (0 for a leaf)
+    value: np.ndarray     # float32 [n_nodes] threshold of an inner node, value of a leaf
+    child: np.ndarray     # int32 [n_nodes]   left child (right = child + 1); a leaf: its own index
+    leaf: np.ndarray      # bool [n_nodes]
+    root: np.ndarray      # int32 [T]
+    base: float = 0.0
+    link: str = "sigmoid"
+    kind: str = "forest"
+
+    def __post_init__(self):
+        self.feat = np.ascontiguousarray(self.feat, np.int32).reshape(-1)
+        self.value = np.ascontiguousarray(self.value, np.float32).reshape(-1)
+        self.child = np.ascontiguousarray(self.child, np.int32).reshape(-1)
+        self.leaf = np.ascontiguousarray(self.leaf, bool).reshape(-1)
+        self.root = np.ascontiguousarray(self.root, np.int32).reshape(-1)
+        self.base = float(self.base)
+        n = self.feat.size
+        if self.link not in LINKS:
+            raise ValueError(f"link must be one of {LINKS}")
+        if not (self.value.size == self.child.size == self.leaf.size == n):
+            raise ValueError("inconsistent node arrays")
+        if self.root.size < 1 or n < 1:
+            raise ValueError("an ensemble needs at least one tree")
+        if n >= MAX_NODES:
+            raise ValueError(f"{n} nodes: the node table holds fewer than 2^24")
+        if self.feat.min() < 0 or self.feat.max() >= N_FEATURES:
+            raise ValueError("feature index out of range")
+        if self.root.min() < 0 or self.root.max() >= n:
+            raise ValueError("root index out of range")
+        idx = np.arange(n, dtype=np.int32)
+        inner = ~self.leaf
+        ci = self.child[inner]
+        if ci.size and (ci.min() < 0 or ci.max() + 1 >= n):
+            raise ValueError("child index out of range")
+        if (ci <= idx[inner]).any():
+            raise ValueError("child indices must point forward (child > node)")
+        self.child = np.where(self.leaf, idx, self.child).astype(np.int32)
+        self.feat = np.where(self.leaf, 0, self.feat).astype(np.int32)
+        parents = np.zeros(n, np.int64)
+        np.add.at(parents, ci, 1)
+        np.add.at(parents, ci + 1, 1)
+        np.add.at(parents, self.root, 1)
+        if (parents > 1).any():
+            raise ValueError("a node is reachable from two parents (or a root is shared / is a child)")
+        # level-by-level expansion from the roots: per-tree depth
+        depth = np.zeros(self.root.size, np.int32)
+        owner = np.full(n, -1, np.int32)              # tree of every reachable node
+        node, tree, level = self.root.copy(), np.arange(self.root.size), 0
+        while True:
+            owner[node] = tree
+            keep = inner[node]
+            node, tree = node[keep], tree[keep]
+            if not node.size:
+                break
+            level += 1
+            if level > MAX_DEPTH:
+                raise ValueError(f"tree depth exceeds {MAX_DEPTH}")
+            depth[tree] = level
+            c = self.child[node]
+            node, tree = np.concatenate([c, c + 1]), np.concatenate([tree, tree])
+        self.tree_depth = depth
+        self.node_tree = owner
+
+    # ------------------------------------------------------------------ shape
+    @property
+    def n_trees(self) -> int:
+        return int(self.root.size)
+
+    @property
+    def depth(self) -> int:
+        return int(self.tree_depth.max())
+
+    @property
+    def n_nodes(self) -> int:
+        return int(self.feat.size)
+
+    def leaf_abs_max(self) -> np.ndarray:
+        """max |leaf value| per tree -- float64 [T] (the scale of float32 summation error)."""
+        out = np.zeros(self.n_trees, np.float64)
+        sel = self.leaf & (self.node_tree >= 0)
+        np.maximum.at(out, self.node_tree[sel], np.abs(self.value[sel].astype(np.float64)))
+        return out
+
+    # ------------------------------------------------------------------ scoring (CPU oracle)
+    def leaf_node(self, X: np.ndarray) -> np.ndarray:
+        """Index of the leaf every (row, tree) ends in -- [n, T]."""
+        X = np.asarray(X, np.float32)
+        cur = np.broadcast_to(self.root[None, :], (X.shape[0], self.n_trees)).astype(np.int64)
+        rows = np.arange(X.shape[0])[:, None]
+        for _ in range(self.depth):
+            right = X[rows, self.feat[cur]] > self.value[cur]      # f32 compare; NaN -> left
+            cur = np.where(self.leaf[cur], cur, self.child[cur] + right)
+        return cur
+
+    def leaf_values(self, X: np.ndarray) -> np.ndarray:
+        """The selected leaf value per tree -- float32 [n, T]."""
+        return self.value[self.leaf_node(X)]
+
+    def raw_score(self, X: np.ndarray) -> np.ndarray:
+        return (self.base + self.leaf_values(X).astype(np.float64).sum(1)).astype(np.float32)
+
+    def predict_proba(self, X: np.ndarray) -> np.ndarray:
+        z = self.raw_score(X)
+        return sigmoid(z) if self.link == "sigmoid" else np.clip(z, 0.0, 1.0).astype(np.float32)
+
+    # ------------------------------------------------------------------ constructors
+    @classmethod
+    def from_oblivious(cls, m: ObliviousGBDT) -> "TreeEnsemble":
+        """Each oblivious tree expanded into a complete general tree with identical outputs
+        (level l of the tree tests split l; NaN thresholds carry over: ``x > NaN`` is false)."""
+        T, D = m.n_trees, m.depth
+        per = (2 << D) - 1
+        L = 1 << D
+        # node at level l, position p (its path bits, first step = most significant)
+        lvl = np.concatenate([np.full(1 << l, l) for l in range(D + 1)])
+        pos = np.concatenate([np.arange(1 << l) for l in range(D + 1)])
+        is_leaf = lvl == D
+        # the oblivious leaf index has the bit of level d at position d: bit-reverse the path
+        rev = np.zeros(L, np.int64)
+        for d in range(D):
+            rev |= ((np.arange(L) >> d) & 1) << (D - 1 - d)
+        feat = np.zeros((T, per), np.int32)
+        value = np.zeros((T, per), np.float32)
+        child = np.zeros((T, per), np.int32)
+        li = np.minimum(lvl, D - 1)
+        feat[:, ~is_leaf] = m.feat[:, li[~is_leaf]]
+        value[:, ~is_leaf] = m.thr[:, li[~is_leaf]]
+        value[:, is_leaf] = m.leaves[:, rev[pos[is_leaf]]]
+        off = np.arange(T, dtype=np.int64)[:, None] * per
+        child[:] = (off + ((2 << lvl) - 1 + 2 * pos)[None, :]).astype(np.int32)
+        return cls(feat.reshape(-1), value.reshape(-1), child.reshape(-1), np.tile(is_leaf, T),
+                   (off[:, 0]).astype(np.int32), float(m.base), "sigmoid")
+
+    @classmethod
+    def random_init(cls, n_trees: int = 16, max_depth: int = 8, p_leaf: float = 0.2, seed: int = 0,
+                    X_ref: Optional[np.ndarray] = None, link: str = "sigmoid") -> "TreeEnsemble":
+        """Random, unbalanced trees: below the root a node becomes a leaf with probability
+        ``p_leaf`` (always at ``max_depth``); thresholds are feature quantiles of ``X_ref``
+        (or N(0,1)) so that splits partition the data.  Reproducible by ``seed``."""
+        rng = np.random.default_rng(seed)
+        qs = None
+        if X_ref is not None:
+            qs = np.quantile(np.asarray(X_ref, np.float32), np.linspace(0.05, 0.95, 19), axis=0).astype(np.float32)
+        feat, value, child, leaf, root = [], [], [], [], []
+
+        def new_node():
+            feat.append(0); value.append(0.0); child.append(0); leaf.append(True)
+            return len(feat) - 1
+
+        for _ in range(n_trees):
+            r = new_node()
+            root.append(r)
+            frontier = [(r, 0)]
+            while frontier:
+                nxt = []
+                for i, d in frontier:
+                    if d == max_depth or (d > 0 and rng.random() < p_leaf):
+                        value[i] = float(rng.standard_normal() * 0.1)
+                        continue
+                    f = int(rng.integers(0, N_FEATURES))
+                    feat[i] = f
+                    value[i] = float(qs[rng.integers(0, qs.shape[0]), f]) if qs is not None else float(rng.standard_normal())
+                    leaf[i] = False
+                    a = new_node()
+                    new_node()
+                    child[i] = a
+                    nxt += [(a, d + 1), (a + 1, d + 1)]
+                frontier = nxt
+        return cls(np.array(feat), np.array(value, np.float32), np.array(child), np.array(leaf), np.array(root),
+                   0.0, link)
+
+    # ------------------------------------------------------------------ device blob
+    def pack(self, wire: bool = False, bins=None) -> bytes:
+        """FRS1 blob (f32 rows; general trees have no W64 / binned-row kernels)."""
+        if wire or bins is not None:
+            raise ValueError("general trees score f32 rows only (no W64 wire rows, no G32 / G20 bins)")
+        w = (self.feat.astype(np.uint32) | (self.leaf.astype(np.uint32) << 5) | (self.child.astype(np.uint32) << 8))
+        node = np.empty((self.n_nodes, 2), np.uint32)
+        node[:, 0] = w
+        node[:, 1] = self.value.view(np.uint32)
+        tree = np.stack([self.root, self.tree_depth], 1).astype(np.int32)
+        blob = header(b"FRS1", 1 if self.link == "sigmoid" else 0, self.n_trees, self.depth, float(self.base),
+                      self.n_nodes)
+        return blob + pad16(tree.tobytes()) + pad16(node.tobytes())
+
+    @classmethod
+    def unpack(cls, blob: bytes) -> "TreeEnsemble":
+        if blob[:4] != b"FRS1":
+            raise ValueError("not an FRS1 blob")
+        flags, T, _depth = struct.unpack_from("<Iii", blob, 4)
+        base = struct.unpack_from("<f", blob, 16)[0]
+        n = struct.unpack_from("<i", blob, 20)[0]
+        off_node = HEADER_BYTES + ((8 * T + 15) & ~15)
+        tree = np.frombuffer(blob, np.int32, 2 * T, HEADER_BYTES).reshape(T, 2)
+        node = np.frombuffer(blob, np.uint32, 2 * n, off_node).reshape(n, 2)
+        w = node[:, 0]
+        m = cls((w & 31).astype(np.int32), node[:, 1].copy().view(np.float32), (w >> 8).astype(np.int32),
+                (w >> 5 & 1).astype(bool), tree[:, 0].copy(), float(base), "sigmoid" if flags & 1 else "identity")
+        if not np.array_equal(m.tree_depth, tree[:, 1]):
+            raise ValueError("FRS1 blob: stored tree depths do not match the node table")
+        return m
+
+    def state_dict(self) -> dict:
+        return {"forest.feat": self.feat, "forest.value": self.value, "forest.child": self.child,
+                "forest.leaf": self.leaf.astype(np.uint8), "forest.root": self.root,
+                "forest.base": np.array([self.base], np.float64),
+                "forest.link": np.array([LINKS.index(self.link)], np.int32)}
+
+    @classmethod
+    def from_state_dict(cls, st: dict) -> "TreeEnsemble":
+        return cls(st["forest.feat"], st["forest.value"], st["forest.child"], np.asarray(st["forest.leaf"]) != 0,
+                   st["forest.root"], float(np.asarray(st["forest.base"]).reshape(-1)[0]),
+                   LINKS[int(np.asarray(st["forest.link"]).reshape(-1)[0])])

@@ -22,8 +22,8 @@ LIB_PATH = _NATIVE / (f"libccfd_hip_{_SAN.replace(',', '_')}.so" if _SAN else "l
 if os.environ.get("CCFD_LIB_PATH"):
     LIB_PATH = Path(os.environ["CCFD_LIB_PATH"]).resolve()
 
-MODEL_LR, MODEL_MLP, MODEL_GBDT = 0, 1, 2
-MODEL_IDS = {"lr": MODEL_LR, "mlp": MODEL_MLP, "gbdt": MODEL_GBDT}
+MODEL_LR, MODEL_MLP, MODEL_GBDT, MODEL_FOREST = 0, 1, 2, 3
+MODEL_IDS = {"lr": MODEL_LR, "mlp": MODEL_MLP, "gbdt": MODEL_GBDT, "forest": MODEL_FOREST}
 N_COUNTER_SLOTS = 64
 ENGINE_FLAG_FULL = 1      # ccfd_abi.h CCFD_ENGINE_FLAG_FULL: drain the flagged ring, call again
 CNT_WIRE_STALE = 4        # ccfd_abi.h CCFD_CNT_WIRE_STALE
@@ -108,6 +108,8 @@ def lib() -> C.CDLL:
         L.ccfd_score_launch.argtypes = [C.POINTER(ScoreArgs), C.c_void_p]
         L.ccfd_score_launch.restype = C.c_int
         L.ccfd_last_error.restype = C.c_char_p
+        L.ccfd_forest_blob_changed.argtypes = [C.c_void_p]
+        L.ccfd_forest_blob_changed.restype = None
         L.ccfd_host_alloc.argtypes = [C.c_size_t]
         L.ccfd_host_alloc.restype = C.c_void_p
         L.ccfd_host_free.argtypes = [C.c_void_p]

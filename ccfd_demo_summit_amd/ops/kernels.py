@@ -28,14 +28,17 @@ class DeviceModel:
         ``bins``: GBDT on binned rows -- ``True`` for the model's own G32 bin table, ``"g20"``
         for the same table on 20-byte G20 rows (<= 31 thresholds a feature), or a
         ``models.gbdt.BinSpec`` containing its thresholds (e.g. the live logs' spec; its
-        ``bits`` select G32 or G20)."""
+        ``bits`` select G32 or G20).  A ``TreeEnsemble`` (kind "forest") takes neither: the
+        general-tree kernel scores f32 rows."""
         self.kind = model.kind
         if self.kind not in MODEL_IDS:
             raise ValueError(f"no device kernel for model kind {self.kind!r}")
         if wire and self.kind not in ("mlp", "lr"):
-            raise ValueError("W64 wire rows are supported by the MLP and LR kernels")
+            raise ValueError("W64 wire rows are supported by the MLP and LR kernels" if self.kind != "forest" else
+                             "general trees (forest) score f32 rows only: no wire=")
         if bins is not None and bins is not False and self.kind != "gbdt":
-            raise ValueError("G32 rows (bins=) are for the GBDT kernel")
+            raise ValueError("G32 rows (bins=) are for the GBDT kernel" if self.kind != "forest" else
+                             "general trees (forest) score f32 rows only: no bins=")
         self.wire = bool(wire)
         if bins is True or bins == "g32":
             bins = model.bin_spec()
@@ -49,6 +52,12 @@ class DeviceModel:
         self.blob = torch.from_numpy(np.frombuffer(packed, np.uint8).copy()).to(device)
         self.trees = getattr(model, "n_trees", 0)
         self.depth = getattr(model, "depth", 0)
+        self._uploaded()
+
+    def _uploaded(self) -> None:
+        # the forest launch caches blob headers by address; this allocation may be a recycled one
+        if self.kind == "forest":
+            lib().ccfd_forest_blob_changed(C.c_void_p(self.blob.data_ptr()))
 
     @classmethod
     def from_blob(cls, kind: str, blob: torch.Tensor, trees: int = 0, depth: int = 0,
@@ -56,6 +65,7 @@ class DeviceModel:
         self = cls.__new__(cls)
         self.kind, self.blob, self.trees, self.depth, self.wire = kind, blob, trees, depth, bool(wire)
         self.bins = bins
+        self._uploaded()
         return self
 
     @property

@@ -124,7 +124,12 @@ def broadcast_blob(ctx: DistContext, blob: Optional[torch.Tensor], src: int = 0,
 def resolve_row_format(kind: str, wire: str = "auto") -> str:
     """Partition-log row format of a model kind: ``auto`` = W64 for the MLP / LR kernels,
     G20 for GBDT (the PCIe-byte-optimal exact or bf16 formats, contracts/transaction.py;
-    ``broadcast_model`` widens G20 -> G32 -> f32 when an ensemble's bin table needs it)."""
+    ``broadcast_model`` widens G20 -> G32 -> f32 when an ensemble's bin table needs it);
+    general trees (``forest``) score f32 rows only."""
+    if kind == "forest":
+        if wire not in ("auto", "f32"):
+            raise ValueError(f"row format {wire} does not apply to model kind forest (f32 rows only)")
+        return "f32"
     if wire == "auto":
         return "g20" if kind == "gbdt" else "w64"
     if (wire == "w64" and kind == "gbdt") or (wire in ("g32", "g20") and kind != "gbdt"):

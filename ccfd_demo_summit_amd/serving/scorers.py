@@ -53,7 +53,7 @@ def make_scorer(model, threshold: float = 0.5, device: str = "auto", **kw):
     if device in ("auto", "gpu"):
         try:
             import torch
-            if torch.cuda.is_available() and getattr(model, "kind", None) in ("lr", "mlp", "gbdt"):
+            if torch.cuda.is_available() and getattr(model, "kind", None) in ("lr", "mlp", "gbdt", "forest"):
                 return GpuScorer(model, threshold, **kw)
         except Exception:
             if device == "gpu":

@@ -8,6 +8,7 @@ the GBDT (train/trainer.py); rank 0 evaluates and writes.
     python -m ccfd_demo_summit_amd.train --model mlp --out model.safetensors
     torchrun --nproc-per-node 2 -m ccfd_demo_summit_amd.train --model gbdt --csv creditcard.csv --out m.st
     python -m ccfd_demo_summit_amd.train --from-catboost model.json --out m.st   # import, no training
+    python -m ccfd_demo_summit_amd.train --from-xgboost model.json --out m.st    # general trees, no training
 """
 from __future__ import annotations
 
@@ -66,7 +67,18 @@ def main(argv=None) -> int:
                          "(+ rank) while training; 0 = off")
     ap.add_argument("--from-catboost", default=None,
                     help="import an oblivious CatBoost JSON model (models/gbdt_import.py) instead of training")
+    ap.add_argument("--from-xgboost", default=None,
+                    help="import an XGBoost JSON model (binary:logistic gbtree, models/xgboost_import.py) as a "
+                         "general tree ensemble instead of training")
     a = ap.parse_args(argv)
+    if a.from_xgboost:
+        from ..models import save_model
+        from ..models.xgboost_import import from_xgboost_json
+        m = from_xgboost_json(a.from_xgboost)
+        save_model(m, a.out, version=a.version)
+        print(json.dumps({"model": "forest", "imported": a.from_xgboost, "out": a.out, "trees": m.n_trees,
+                          "depth": m.depth, "nodes": m.n_nodes}), flush=True)
+        return 0
     if a.from_catboost:
         from ..models import save_model
         from ..models.gbdt_import import from_catboost_json

@@ -259,6 +259,7 @@ class Engine {
     if (cfg.wire < 0 || cfg.wire > 3) { set_error("wire must be 0 (f32), 1 (W64), 2 (G32) or 3 (G20)"); return -1; }
     if (cfg.wire == 1 && cfg.model == CCFD_MODEL_GBDT) { set_error("W64 wire rows: MLP and LR only"); return -1; }
     if (cfg.wire >= 2 && cfg.model != CCFD_MODEL_GBDT) { set_error("G32 / G20 rows: GBDT only"); return -1; }
+    if (cfg.wire != 0 && cfg.model == CCFD_MODEL_FOREST) { set_error("forest models score f32 rows only"); return -1; }
     rowf = cfg.wire == 3 ? CCFD_G20_ROW_BYTES / 4 : cfg.wire == 2 ? CCFD_G32_ROW_BYTES / 4
          : cfg.wire ? CCFD_WIRE_ROW_BYTES / 4 : CCFD_N_FEATURES;
     amount_f = cfg.wire >= 2 ? -1 : cfg.wire ? CCFD_WIRE_ROW_BYTES / 4 - 1 : CCFD_N_FEATURES - 1;
@@ -365,7 +366,9 @@ class Engine {
   int persist_init() {
     const bool g32 = cfg.model == CCFD_MODEL_GBDT && cfg.wire >= 2;     // G32 or G20 rows
     if (cfg.model != CCFD_MODEL_MLP && cfg.model != CCFD_MODEL_LR && !g32) {
-      set_error("persistent exec_mode supports the MLP and LR models, and GBDT on G32 / G20 rows");
+      set_error(cfg.model == CCFD_MODEL_FOREST
+                    ? "persistent exec_mode has no general-tree (forest) kernel: use exec_mode launch"
+                    : "persistent exec_mode supports the MLP and LR models, and GBDT on G32 / G20 rows");
       return -1;
     }
     if (cfg.output_mode != 0 || cfg.depth > CCFD_PERSIST_MAX_RING) {

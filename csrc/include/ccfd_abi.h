@@ -10,7 +10,9 @@
 extern "C" {
 #endif
 
-enum ccfd_model_kind { CCFD_MODEL_LR = 0, CCFD_MODEL_MLP = 1, CCFD_MODEL_GBDT = 2 };
+// CCFD_MODEL_FOREST: general (non-oblivious) tree ensembles, f32 rows, launch path only;
+// gbdt_trees / gbdt_depth carry its tree count and maximum depth (models/forest.py).
+enum ccfd_model_kind { CCFD_MODEL_LR = 0, CCFD_MODEL_MLP = 1, CCFD_MODEL_GBDT = 2, CCFD_MODEL_FOREST = 3 };
 
 // Cumulative u64 counter slots written by the scoring kernels' epilogue (device side)
 // and all-reduced across ranks (X2 in SURVEY.md §2.4).  Mirrors ops/layout.py.
@@ -88,8 +90,8 @@ typedef struct ccfd_score_args {
   int32_t model;         // ccfd_model_kind
   const void* blob;      // packed model (device memory), see models/*.py pack()
   float threshold;       // FRAUD_THRESHOLD
-  int32_t gbdt_trees;    // GBDT only
-  int32_t gbdt_depth;    // GBDT only
+  int32_t gbdt_trees;    // GBDT / forest: trees
+  int32_t gbdt_depth;    // GBDT: depth; forest: maximum depth
   int32_t flags;         // CCFD_ARG_* (informational)
   float* proba;          // out [n] proba_1 (device or host-mapped), may be NULL
   uint8_t* route;        // out [n] 1 = fraud route, may be NULL
@@ -134,6 +136,10 @@ int ccfd_score_launch_multi(const ccfd_multi_args* m, void* stream);
 // counters/histogram) on `stream` (a hipStream_t; NULL = legacy default stream).
 // Returns 0 or a negative error code (shape/alignment checks happen on the host).
 int ccfd_score_launch(const ccfd_score_args* a, void* stream);
+// CCFD_MODEL_FOREST launches size their LDS from the blob's header, read from device memory
+// once per blob address.  Call this after writing another forest blob to an address the
+// library has launched with before (a recycled allocation).
+void ccfd_forest_blob_changed(const void* blob);
 
 // ---------------------------------------------------------------------------
 // Persistent streaming kernel (exec_mode = 1): ONE long-running launch per engine; the

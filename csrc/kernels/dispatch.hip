@@ -12,6 +12,7 @@ int launch_lr(const ccfd_score_args& a, hipStream_t s);
 int launch_lr_multi(const ccfd_multi_args& m, hipStream_t s);
 int launch_gbdt(const ccfd_score_args& a, hipStream_t s);
 int launch_gbdt_g32(const ccfd_score_args& a, hipStream_t s);
+int launch_forest(const ccfd_score_args& a, hipStream_t s);
 
 thread_local std::string g_last_error;
 void set_error(const std::string& e) { g_last_error = e; }
@@ -26,6 +27,10 @@ int ccfd_score_launch(const ccfd_score_args* a, void* stream) {
   if (a == nullptr || a->blob == nullptr || a->x == nullptr) { set_error("null argument"); return -1; }
   if (a->n < 0) { set_error("n < 0"); return -1; }
   if (a->n == 0) return 0;
+  if (a->model == CCFD_MODEL_FOREST && (a->flags & (CCFD_ARG_WIRE_W64 | CCFD_ARG_WIRE_G32 | CCFD_ARG_WIRE_G20))) {
+    set_error("forest kernel: f32 rows only (no W64 / G32 / G20 rows)");
+    return -3;
+  }
   if (a->flags & CCFD_ARG_WIRE_G32) {
     if (a->model != CCFD_MODEL_GBDT) { set_error("G32 rows: GBDT kernel only"); return -3; }
     const bool g20 = (a->flags & CCFD_ARG_WIRE_G20) != 0;     // dword loads: 4-byte aligned rows
@@ -51,6 +56,10 @@ int ccfd_score_launch(const ccfd_score_args* a, void* stream) {
     case CCFD_MODEL_LR: rc = launch_lr(*a, s); break;
     case CCFD_MODEL_MLP: rc = launch_mlp(*a, s); break;
     case CCFD_MODEL_GBDT: rc = launch_gbdt(*a, s); break;
+    case CCFD_MODEL_FOREST:
+      rc = launch_forest(*a, s);
+      if (rc == -2) return rc;          // shape refused before any launch; message already set
+      break;
     default: set_error("unknown model kind"); return -2;
   }
   if (rc != 0) {
