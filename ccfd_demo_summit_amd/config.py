@@ -98,6 +98,7 @@ class EngineConfig:
     ingest_threads: int = 0          # native Kafka consumer threads per rank (partitions split; 0 = auto:
                                      # one per partition for GBDT's binned rows, else 1)
     model_watch: str = ""            # hot-swap when this safetensors file changes (rank 0)
+    shadow_model: str = ""           # challenger MLP (safetensors) scored beside the live model, counters only
     output_mode: str = "zerocopy"    # zerocopy (kernel writes pinned host) | dma
     exec_mode: str = "auto"          # persistent | launch | auto (persistent for zero-copy in/out:
                                      # the mode bench.py measures; launch_/engine_service.py)
@@ -152,6 +153,7 @@ ENV_MAP = {
     "CCFD_WIRE": ("engine", "wire", str),
     "CCFD_COALESCE": ("engine", "coalesce", int),
     "CCFD_MODEL_WATCH": ("engine", "model_watch", str),
+    "CCFD_SHADOW_MODEL": ("engine", "shadow_model", str),
     "CCFD_INPUT_MODE": ("engine", "input_mode", str),
     "CCFD_OUTPUT_MODE": ("engine", "output_mode", str),
     "CCFD_EXEC_MODE": ("engine", "exec_mode", str),

@@ -18,7 +18,9 @@ import torch
 
 from ..ops._lib import (BATCH_TRACE_DTYPE, BIN_FORMATS, ENGINE_FLAG_FULL, FLAGGED_DTYPE, SCORED_DTYPE, MODEL_IDS,
                         N_COUNTER_SLOTS, ROW_FORMATS, EngineConfig, EngineStats, Flagged, check, last_error, lib)
-from ..ops.kernels import ROW_BYTES, DeviceModel
+from ..ops._lib import (CNT_SHADOW_ABSDIFF_E6, CNT_SHADOW_BOTH, CNT_SHADOW_FRAUD, CNT_SHADOW_PROBA_E6,
+                        CNT_SHADOW_ROWS)
+from ..ops.kernels import ROW_BYTES, DeviceModel, check_shadow_pair
 
 N_FEATURES = 30
 WIRE_ROW_F32 = 16            # W64 wire row = 64 B = 16 f32 words (contracts.transaction)
@@ -310,7 +312,8 @@ class StreamEngine:
     def __init__(self, dm: DeviceModel, batch: int = 4096, depth: int = 8, streams: int = 2,
                  input_mode: str = "dma", output_mode: str = "zerocopy", threshold: float = 0.5,
                  device: Optional[int] = None, flag_capacity: int = 1 << 20, exec_mode: str = "launch",
-                 persist_grid: int = 0, coalesce: int = 1, rules=None, persist_items: str = "auto"):
+                 persist_grid: int = 0, coalesce: int = 1, rules=None, persist_items: str = "auto",
+                 shadow: Optional[DeviceModel] = None):
         """exec_mode: "launch" = one fused kernel launch per micro-batch; "persistent" = one
         long-running kernel fed through a descriptor ring (MLP/LR, zero-copy outputs; general
         trees -- kind "forest" -- have a launch-mode kernel only).
@@ -322,7 +325,15 @@ class StreamEngine:
         coalesce: launch mode -- up to this many ready, log-contiguous micro-batches go out as
         one launch (MLP, zero-copy in/out); completion stays per micro-batch.
         rules: a compiled routing rule set (ops.kernels.DeviceRules) evaluated per row in the
-        kernels' epilogue instead of ``proba >= threshold`` (kept alive by the engine)."""
+        kernels' epilogue instead of ``proba >= threshold`` (kept alive by the engine).
+        shadow: a challenger MLP scored beside ``dm`` on the same rows in the same kernel pass
+        (``set_shadow``); the engine publishes its results as counters only
+        (``shadow_counters``).  MLP on W64 rows, threshold route, claimed persistent items of
+        128 / 256 / 512 rows; while one is set a launch-mode engine submits one launch per
+        micro-batch (``coalesce`` is not applied)."""
+        if shadow is not None:           # refused before the native engine exists
+            check_shadow_pair(dm, shadow, rules=rules, persist_items=2 if persist_items == "pipelined" else 0)
+        self.shadow: Optional[DeviceModel] = None
         self.dm = dm
         self.device = torch.device("cuda", device if device is not None else torch.cuda.current_device())
         self.batch = int(batch)
@@ -374,6 +385,12 @@ class StreamEngine:
         # the flagged drains may run on a collector thread beside the pump (FlaggedDrainer):
         # the ring's native drain is lock-protected, the stash and the copy-out are guarded here
         self._drain_lock = threading.Lock()
+        if shadow is not None:
+            try:
+                self.set_shadow(shadow)
+            except Exception:
+                self.close()
+                raise
 
     def close(self):
         if getattr(self, "h", None):
@@ -489,6 +506,41 @@ class StreamEngine:
                    "ccfd_engine_set_blob")
         self.dm = dm                     # keeps the new blob alive; the old one may be freed now
         self.model_version = getattr(self, "model_version", 0) + 1
+
+    def set_shadow(self, dm: Optional[DeviceModel]) -> None:
+        """Score ``dm`` (a challenger MLP, W64 blob) beside the champion from the next
+        micro-batch on, or stop doing so (``None``).  Like ``swap_model``: in-flight
+        micro-batches finish first.  The shadow's results are the ``CNT_SHADOW_*`` slots of the
+        epoch counters (``shadow_counters``); the engine keeps ``dm`` alive."""
+        if dm is not None:
+            check_shadow_pair(self.dm, dm, rules=self.rules,
+                              persist_items=2 if self.persist_items == "pipelined" else 0)
+        ptr = C.c_void_p(dm.blob.data_ptr()) if dm is not None else None
+        self._call(lambda: lib().ccfd_engine_set_shadow(C.c_void_p(self.h), ptr), "ccfd_engine_set_shadow")
+        self.shadow = dm                 # keeps the blob alive; the previous one may be freed now
+
+    @staticmethod
+    def shadow_counters(c) -> Dict[str, float]:
+        """Champion-vs-shadow summary of a counter vector (an epoch buffer, an all-reduced sum,
+        or their running total): rows the shadow scored, rows it routes as fraud, rows both
+        route as fraud, route disagreements, the shadow's mean proba_1 and the mean
+        |proba_1 - shadow proba_1|."""
+        v = c.detach().cpu().numpy() if isinstance(c, torch.Tensor) else np.asarray(c)
+        rows, fraud, both = int(v[CNT_SHADOW_ROWS]), int(v[CNT_SHADOW_FRAUD]), int(v[CNT_SHADOW_BOTH])
+        # slot 1 counts every row the champion flagged; with a shadow set for the whole window
+        # fraud + shadow_fraud - 2 * both is the number of rows the two route differently
+        disagree = int(v[1]) + fraud - 2 * both if rows else 0
+        return {"rows": rows, "fraud": fraud, "both": both, "disagree": disagree,
+                "mean_proba": int(v[CNT_SHADOW_PROBA_E6]) * 1e-6 / rows if rows else 0.0,
+                "mean_abs_diff": int(v[CNT_SHADOW_ABSDIFF_E6]) * 1e-6 / rows if rows else 0.0}
+
+    def promote_shadow(self) -> None:
+        """Make the shadow the champion (``swap_model``) and stop shadow scoring."""
+        if self.shadow is None:
+            raise ValueError("no shadow model set")
+        dm = self.shadow
+        self.swap_model(dm)
+        self.set_shadow(None)
 
     def epoch_complete(self, flip_count: int) -> bool:
         """True once every micro-batch submitted before flip number ``flip_count`` completed."""

@@ -359,6 +359,23 @@ def _rank_path(path: str, rank: int) -> str:
     return f"{root}.rank{rank}{ext or '.jsonl'}"
 
 
+def engine_service_settings(a, cfg):
+    """The engine service's settings from the parsed command line and the configuration
+    (a flag wins over its config / environment equivalent)."""
+    from .engine_service import EngineServiceConfig
+    return EngineServiceConfig(
+        topic=cfg.kafka.transactions_topic, group_id=cfg.kafka.group_id, batch=cfg.engine.batch,
+        depth=cfg.engine.depth, streams=cfg.engine.streams, input_mode=cfg.engine.input_mode,
+        output_mode=cfg.engine.output_mode, exec_mode=cfg.engine.exec_mode,
+        flush_us=cfg.engine.max_delay_us, reduce_period_ms=cfg.engine.reduce_period_ms,
+        threshold=cfg.router.fraud_threshold, coalesce=cfg.engine.coalesce,
+        ingest_threads=cfg.engine.ingest_threads, persist_items=cfg.engine.persist_items,
+        standard_mode=cfg.router.standard_mode, scored_capacity=cfg.engine.scored_capacity,
+        native_serve=cfg.engine.native_serve,
+        model_watch=(a.watch_model or cfg.engine.model_watch or None),
+        shadow_model=(a.shadow_model or cfg.engine.shadow_model or None))
+
+
 def cmd_engine(a, cfg):
     import numpy as np
     import torch
@@ -371,7 +388,7 @@ def cmd_engine(a, cfg):
     from ..router.router import Router
     from ..router.rules import RuleSet
     from ..utils.numa import bind_to_gpu
-    from .engine_service import EngineService, EngineServiceConfig, rule_safe_row_format
+    from .engine_service import EngineService, rule_safe_row_format
     ctx = init_distributed()
     bind_to_gpu(ctx.device.index)
     rules = RuleSet.from_config(cfg.router)
@@ -397,16 +414,17 @@ def cmd_engine(a, cfg):
         handoff = ShardedHandoff(kie.clients, dlqs, capacity=cfg.engine.handoff_capacity,
                                  workers=cfg.engine.handoff_workers)
     router = Router(rules, kie, hub.router, standard_mode=cfg.router.standard_mode, handoff=handoff)
-    svc = EngineService(ctx, dm, broker, router, EngineServiceConfig(
-        topic=cfg.kafka.transactions_topic, group_id=cfg.kafka.group_id, batch=cfg.engine.batch,
-        depth=cfg.engine.depth, streams=cfg.engine.streams, input_mode=cfg.engine.input_mode,
-        output_mode=cfg.engine.output_mode, exec_mode=cfg.engine.exec_mode,
-        flush_us=cfg.engine.max_delay_us, reduce_period_ms=cfg.engine.reduce_period_ms,
-        threshold=cfg.router.fraud_threshold, coalesce=cfg.engine.coalesce,
-        ingest_threads=cfg.engine.ingest_threads, persist_items=cfg.engine.persist_items,
-        standard_mode=cfg.router.standard_mode, scored_capacity=cfg.engine.scored_capacity,
-        native_serve=cfg.engine.native_serve,
-        model_watch=(a.watch_model or cfg.engine.model_watch or None))).start()
+    settings = engine_service_settings(a, cfg)
+    shadow = None
+    if settings.shadow_model:
+        # the challenger: loaded on rank 0, broadcast like the live model so every rank scores
+        # the same blob; set before streaming starts (refused unless both are MLPs on W64 rows)
+        from ..models import load_model
+        shadow = broadcast_model(ctx, load_model(settings.shadow_model) if ctx.rank == 0 else None,
+                                 cfg.engine.model, dm.row_format)
+        print(f"[engine] shadow model {settings.shadow_model}: scored beside the live model, counters only",
+              flush=True)
+    svc = EngineService(ctx, dm, broker, router, settings, shadow=shadow).start()
     hub.gpu_registry.register(GpuEngineCollector(svc.metrics_source, rank_label=str(ctx.rank)))
     # the process's node-local rank (torchrun LOCAL_RANK) -- not the device index, which a
     # several-ranks-per-GPU rehearsal (CCFD_DEVICE_MODULO) maps onto the same GPU
@@ -694,6 +712,9 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--host", default="0.0.0.0")
     ap.add_argument("--port", type=int, default=None)
     ap.add_argument("--watch-model", default=None, help="engine: hot-swap weights when this file changes")
+    ap.add_argument("--shadow-model", default=None,
+                    help="engine: safetensors MLP scored beside the live model on the same rows "
+                         "(shadow counters and ccfd_gpu_shadow_* series only; promote it with --watch-model)")
     ap.add_argument("--model-metrics-port", type=int, default=None,
                     help="engine: port (+ local rank) of the model's /prometheus (proba_1 / Amount / V17 / V10, "
                          "seldon_api_engine_*); default SELDON port 8000, 0 = off")

@@ -74,6 +74,8 @@ class EngineServiceConfig:
                                      # for the GIL between run() calls (profiles/r4/tail/)
     serve_budget_us: int = 200       # native serving thread: run() budget per iteration
     model_watch: Optional[str] = None   # rank 0: hot-swap when this safetensors file changes
+    shadow_model: Optional[str] = None  # file the shadow (challenger) model was loaded from; the
+                                        # packed model itself is EngineService(shadow=)
     handoff_hold_low: float = 0.5    # a held (full) hand-off queue resumes scoring below this fill
     standard_mode: str = "count"     # "process": every standard-routed row is handed to the router
                                      # (scored-record ring) to start a standard process
@@ -111,7 +113,11 @@ def resolve_exec_mode(exec_mode: str, model_kind: str, row_format: str, input_mo
 
 
 class EngineService:
-    def __init__(self, ctx, dm, broker, router, cfg: EngineServiceConfig, reducer=None, partitions=None):
+    def __init__(self, ctx, dm, broker, router, cfg: EngineServiceConfig, reducer=None, partitions=None,
+                 shadow=None):
+        """``shadow``: a challenger DeviceModel (MLP, W64 rows) scored beside ``dm`` from the
+        first micro-batch on; its results are the shadow counter slots of the X2 all-reduce and
+        the ``ccfd_gpu_shadow_*`` series (engine.StreamEngine.set_shadow)."""
         from ..engine import StreamEngine
         from ..parallel.dp import CounterReducer, EpochPipeline, assign_partitions, x_group
         self.ctx = ctx
@@ -135,7 +141,7 @@ class EngineService:
         self.engine = StreamEngine(dm, batch=cfg.batch, depth=cfg.depth, streams=cfg.streams,
                                    input_mode=cfg.input_mode, output_mode=cfg.output_mode, threshold=threshold,
                                    device=ctx.device.index, exec_mode=self.exec_mode, coalesce=cfg.coalesce,
-                                   rules=self.device_rules, persist_items=cfg.persist_items)
+                                   rules=self.device_rules, persist_items=cfg.persist_items, shadow=shadow)
         if cfg.standard_mode not in ("count", "process"):
             raise ValueError("standard_mode must be 'count' or 'process'")
         self.standard_mode = cfg.standard_mode

@@ -276,6 +276,22 @@ class GpuEngineCollector:
             h.add_metric([label], [(str(b) if b != float("inf") else "+Inf", float(c)) for b, c in zip(bounds, cum)],
                          sum_value=float("nan"))
         yield h
+        # shadow (challenger) model, slots 40..44: only while one has scored rows, so the
+        # exposition of an engine without a shadow is unchanged.  The two *_sum series are
+        # sums of probabilities (divide by shadow_rows_total for the means).
+        if cnt.size > 44 and cnt[40] > 0:
+            for name, doc, v in (("shadow_rows", "Rows the shadow model scored", float(cnt[40])),
+                                 ("shadow_fraud", "Rows the shadow model routes as fraud", float(cnt[41])),
+                                 ("shadow_both_fraud", "Rows champion and shadow both route as fraud",
+                                  float(cnt[42]))):
+                c = CounterMetricFamily(M.GPU_PREFIX + name, doc, labels=["rank"])
+                c.add_metric([self.rank_label], v)
+                yield c
+            for name, doc, v in (("shadow_proba_sum", "Sum of the shadow model's proba_1", float(cnt[43]) * 1e-6),
+                                 ("shadow_abs_diff_sum", "Sum of |proba_1 - shadow proba_1|", float(cnt[44]) * 1e-6)):
+                g = GaugeMetricFamily(M.GPU_PREFIX + name, doc, labels=["rank"])
+                g.add_metric([self.rank_label], v)
+                yield g
         if lat is not None and np.asarray(lat).sum() > 0:
             q = GaugeMetricFamily(M.GPU_BATCH_LATENCY.replace("_seconds", "_quantile_seconds"),
                                   "Micro-batch latency quantiles", labels=["quantile"])

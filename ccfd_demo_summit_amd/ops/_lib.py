@@ -27,6 +27,8 @@ MODEL_IDS = {"lr": MODEL_LR, "mlp": MODEL_MLP, "gbdt": MODEL_GBDT, "forest": MOD
 N_COUNTER_SLOTS = 64
 ENGINE_FLAG_FULL = 1      # ccfd_abi.h CCFD_ENGINE_FLAG_FULL: drain the flagged ring, call again
 CNT_WIRE_STALE = 4        # ccfd_abi.h CCFD_CNT_WIRE_STALE
+# ccfd_abi.h CCFD_CNT_SHADOW_*: the challenger's counters (zero while no shadow model is set)
+CNT_SHADOW_ROWS, CNT_SHADOW_FRAUD, CNT_SHADOW_BOTH, CNT_SHADOW_PROBA_E6, CNT_SHADOW_ABSDIFF_E6 = 40, 41, 42, 43, 44
 ARG_WIRE_W64, ARG_WIRE_G32, ARG_WIRE_G20 = 2, 4, 8
 ROW_FORMATS = {"f32": 0, "w64": 1, "g32": 2, "g20": 3}      # ccfd_engine_config.wire
 BIN_FORMATS = ("g32", "g20")                                # rows of per-feature bins (GBDT)
@@ -39,6 +41,22 @@ class ScoreArgs(C.Structure):
                 ("route", C.c_void_p), ("counters", C.c_void_p), ("slot_ctl", C.c_void_p),
                 ("flag_idx", C.c_void_p), ("done_rec", C.c_void_p), ("done_seq", C.c_uint64),
                 ("rules", C.c_void_p)]
+
+
+class ShadowArgs(C.Structure):           # ccfd_shadow_args
+    _fields_ = [("base", ScoreArgs), ("shadow_blob", C.c_void_p), ("shadow_proba", C.c_void_p)]
+
+
+class PersistArgs(C.Structure):          # ccfd_persist_args
+    _fields_ = [("ctl", C.c_void_p), ("desc", C.c_void_p), ("dev", C.c_void_p), ("ring", C.c_int32),
+                ("items_per_batch", C.c_int32), ("model", C.c_int32), ("threshold", C.c_float),
+                ("tiles_per_wave", C.c_int32), ("flags", C.c_int32), ("blob", C.c_void_p),
+                ("counters", C.c_void_p * 2), ("rules", C.c_void_p), ("gbdt_trees", C.c_int32),
+                ("gbdt_depth", C.c_int32)]
+
+
+class PersistShadowArgs(C.Structure):    # ccfd_persist_shadow_args
+    _fields_ = [("base", PersistArgs), ("shadow_blob", C.c_void_p)]
 
 
 class EngineConfig(C.Structure):
@@ -108,6 +126,10 @@ def lib() -> C.CDLL:
         L.ccfd_score_launch.argtypes = [C.POINTER(ScoreArgs), C.c_void_p]
         L.ccfd_score_launch.restype = C.c_int
         L.ccfd_last_error.restype = C.c_char_p
+        L.ccfd_score_launch_shadow.argtypes = [C.POINTER(ShadowArgs), C.c_void_p]
+        L.ccfd_score_launch_shadow.restype = C.c_int
+        L.ccfd_persist_launch_shadow.argtypes = [C.POINTER(PersistShadowArgs), C.c_int, C.c_void_p]
+        L.ccfd_persist_launch_shadow.restype = C.c_int
         L.ccfd_forest_blob_changed.argtypes = [C.c_void_p]
         L.ccfd_forest_blob_changed.restype = None
         L.ccfd_host_alloc.argtypes = [C.c_size_t]
@@ -125,6 +147,7 @@ def lib() -> C.CDLL:
         L.ccfd_engine_flip_epoch.argtypes = [C.c_void_p, C.c_void_p]
         L.ccfd_engine_epoch_complete.argtypes = [C.c_void_p, C.c_int64]
         L.ccfd_engine_set_blob.argtypes = [C.c_void_p, C.c_void_p]
+        L.ccfd_engine_set_shadow.argtypes = [C.c_void_p, C.c_void_p]
         L.ccfd_engine_drain_flagged.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         L.ccfd_engine_drain_flagged.restype = C.c_int64
         L.ccfd_engine_scored_enable.argtypes = [C.c_void_p, C.c_int64]

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from ._lib import (ARG_WIRE_G20, ARG_WIRE_G32, ARG_WIRE_W64, BIN_FORMATS, MODEL_IDS, N_COUNTER_SLOTS, ScoreArgs,
-                   check, lib)
+                   ShadowArgs, check, lib)
 
 N_FEATURES = 30
 ROW_BYTES = {"f32": 4 * N_FEATURES, "w64": 64, "g32": 32, "g20": 20}
@@ -98,14 +98,46 @@ def new_counters(device="cuda") -> torch.Tensor:
     return torch.zeros(N_COUNTER_SLOTS, dtype=torch.int64, device=device)
 
 
+def check_shadow_pair(dm: DeviceModel, shadow: DeviceModel, rules=None, persist_items: int = 0) -> None:
+    """Refuse (``ValueError`` naming the combination) every champion / shadow pair the shadow
+    kernels do not cover: both must be MLPs packed for W64 rows (``DeviceModel(..., wire=True)``),
+    routed by ``proba >= threshold`` (no ``rules``), and a persistent engine must use claimed
+    items (``persist_items`` 0 / 1, not the pipelined 2).  Pure host check: no launch, no GPU."""
+    from ..models.mlp import WIRE_BLOB_BYTES
+    if dm.kind != shadow.kind:
+        raise ValueError(f"shadow model: kind mismatch, champion is {dm.kind!r} and shadow is {shadow.kind!r} "
+                         "(a shadow is a candidate for swap_model: same kind and shape)")
+    if dm.kind != "mlp":
+        raise ValueError(f"shadow model: {dm.kind!r} models have no shadow kernel (MLP on W64 rows only)")
+    for role, m in (("champion", dm), ("shadow", shadow)):
+        if m.row_format != "w64":
+            raise ValueError(f"shadow model: the {role} MLP is packed for {m.row_format} rows; "
+                             "both blobs must be packed for W64 rows (DeviceModel(..., wire=True))")
+        if m.blob.numel() * m.blob.element_size() != WIRE_BLOB_BYTES:
+            raise ValueError(f"shadow model: the {role} blob is not a {WIRE_BLOB_BYTES}-byte W64 MLP blob")
+    if rules is not None:
+        raise ValueError("shadow model: routing rules present; a shadow routes by proba >= threshold only")
+    if int(persist_items) == 2:
+        raise ValueError("shadow model: pipelined persistent items (persist_items=2 / \"pipelined\") have no "
+                         "shadow kernel; use claimed items")
+
+
 def score(dm: DeviceModel, x: torch.Tensor, threshold: float = 0.5,
           proba: Optional[torch.Tensor] = None, route: Optional[torch.Tensor] = None,
           counters: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
-          flags: int = 0, rules: Optional[DeviceRules] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+          flags: int = 0, rules: Optional[DeviceRules] = None, shadow: Optional[DeviceModel] = None,
+          shadow_proba: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, ...]:
     """Fused score of x [n,30] (float32, CUDA) -- or, for a ``wire`` model, W64 rows
     ([n,64] uint8 or [n,16] float32 view), for a ``bins`` model G32 / G20 rows ([n,32] / [n,20] u8) --
     returns (proba_1 [n] f32, route [n] u8).
-    ``flags``: extra ``CCFD_ARG_*`` bits (ablation switches for profiling)."""
+    ``flags``: extra ``CCFD_ARG_*`` bits (ablation switches for profiling).
+    ``shadow``: a challenger MLP (W64 blob, like ``dm``) scored on the same rows in the same
+    pass; returns (proba_1, route, shadow proba_1 [n] f32) and adds the ``CNT_SHADOW_*``
+    counters (``check_shadow_pair`` lists what is refused)."""
+    if shadow is not None:
+        check_shadow_pair(dm, shadow, rules=rules)
+    elif shadow_proba is not None:
+        raise ValueError("shadow_proba= without shadow=")
     fmt = dm.row_format
     wire = fmt != "f32"
     if wire:
@@ -138,5 +170,17 @@ def score(dm: DeviceModel, x: torch.Tensor, threshold: float = 0.5,
     a.counters = counters.data_ptr() if counters is not None else None
     a.rules = rules.ptr if rules is not None else None
     s = stream if stream is not None else torch.cuda.current_stream(x.device)
+    if shadow is not None:
+        if shadow_proba is None:
+            shadow_proba = torch.empty(n, dtype=torch.float32, device=x.device)
+        elif not shadow_proba.is_cuda or shadow_proba.dtype != torch.float32 or shadow_proba.numel() < n or \
+                not shadow_proba.is_contiguous():
+            raise ValueError("shadow_proba must be a contiguous CUDA float32 tensor of at least n elements")
+        sa = ShadowArgs()
+        sa.base = a
+        sa.shadow_blob = shadow.blob.data_ptr()
+        sa.shadow_proba = shadow_proba.data_ptr()
+        check(lib().ccfd_score_launch_shadow(C.byref(sa), C.c_void_p(s.cuda_stream)), "ccfd_score_launch_shadow")
+        return proba, route, shadow_proba
     check(lib().ccfd_score_launch(C.byref(a), C.c_void_p(s.cuda_stream)), "ccfd_score_launch")
     return proba, route

@@ -360,6 +360,7 @@ class Engine {
   int persist_C = 0;
   int persist_tpw = 1;
   bool persist_pipe = false;
+  const void* shadow_blob = nullptr;       // challenger MLP scored beside cfg.blob (set_shadow)
   int64_t completed_upto = 0;              // batches completed in order (seq count)
   std::vector<int64_t> flip_seq;           // seq at each epoch flip
 
@@ -505,7 +506,15 @@ class Engine {
                      : (wire_flag & CCFD_ARG_WIRE_W64) ? CCFD_PERSIST_GRID_W64
                      : big_trees ? 4 * CCFD_PERSIST_GRID
                      : (wire_flag & CCFD_ARG_WIRE_G20) ? CCFD_PERSIST_GRID_G20 : CCFD_PERSIST_GRID;
-    int rc = ccfd_persist_launch(&a, grid, pstream);
+    int rc;
+    if (shadow_blob) {
+      ccfd_persist_shadow_args sa{};
+      sa.base = a;
+      sa.shadow_blob = shadow_blob;
+      rc = ccfd_persist_launch_shadow(&sa, grid, pstream);
+    } else {
+      rc = ccfd_persist_launch(&a, grid, pstream);
+    }
     if (rc) { set_error("persistent kernel launch failed"); return rc; }
     prunning = true;
     return 0;
@@ -894,7 +903,15 @@ class Engine {
       a.flags = (coherent_out ? CCFD_ARG_FENCE_COHERENT : CCFD_ARG_FENCE_SYS);
     }
     a.flags |= wire_flag;
-    int rc = ccfd_score_launch(&a, stream);
+    int rc;
+    if (shadow_blob) {                  // counters only: no per-row shadow output in the slots
+      ccfd_shadow_args sa{};
+      sa.base = a;
+      sa.shadow_blob = shadow_blob;
+      rc = ccfd_score_launch_shadow(&sa, stream);
+    } else {
+      rc = ccfd_score_launch(&a, stream);
+    }
     if (rc) return rc;
     if (debug_sync) HIPCHK(hipStreamSynchronize(stream));   // CCFD_DEBUG_SYNC: fault -> this batch
     if (cfg.output_mode == 1) {
@@ -910,7 +927,8 @@ class Engine {
   // that are contiguous in one partition's log go out as ONE kernel launch; each keeps its
   // own slot, outputs, flag list and kernel-published completion record.
   int coalesce_max() const {
-    if (persistent || cfg.input_mode != 1 || cfg.output_mode != 0 ||
+    // a shadow model is scored by the single-launch shadow kernel: one launch per micro-batch
+    if (persistent || shadow_blob || cfg.input_mode != 1 || cfg.output_mode != 0 ||
         (cfg.model != CCFD_MODEL_MLP && cfg.model != CCFD_MODEL_LR)) return 1;
     return std::max(1, std::min({cfg.coalesce, CCFD_MAX_SUB, (int)slots.size()}));
   }
@@ -1102,6 +1120,44 @@ class Engine {
     if (rc) return rc;
     if (persistent && prunning) { rc = persist_halt(); if (rc) return rc; }
     cfg.blob = blob;
+    return 0;
+  }
+
+  // Shadow (challenger) model, nullptr = none.  Same hand-over as set_blob; the combinations
+  // the shadow kernels do not cover are refused here, before anything is drained or launched.
+  int set_shadow(const void* blob) {
+    if (blob != nullptr) {
+      static const char* const kKind[] = {"lr", "mlp", "gbdt", "forest"};
+      if (cfg.model != CCFD_MODEL_MLP) {
+        set_error(std::string("shadow model refused: the engine's champion is ") +
+                  (cfg.model >= 0 && cfg.model < 4 ? kKind[cfg.model] : "unknown") +
+                  "; only an MLP champion on W64 rows can carry a shadow");
+        return -1;
+      }
+      if (cfg.wire != 1) {
+        set_error("shadow model refused: the engine scores an MLP on f32 rows; shadow scoring needs W64 rows");
+        return -1;
+      }
+      if (cfg.rules != nullptr) {
+        set_error("shadow model refused: the engine routes by a rule program; shadow scoring routes by threshold only");
+        return -1;
+      }
+      if (persistent && persist_pipe) {
+        set_error("shadow model refused: pipelined persistent items (persist_items = 2 / CCFD_PERSIST_PIPE) "
+                  "have no shadow kernel; use claimed items");
+        return -1;
+      }
+      if (persistent && persist_tpw != 2 && persist_tpw != 4 && persist_tpw != 8) {
+        set_error("shadow model refused: persistent items of " + std::to_string(64 * persist_tpw) +
+                  " rows; the shadow kernel takes items of 128, 256 or 512 rows");
+        return -1;
+      }
+    }
+    HIPCHK(hipSetDevice(cfg.device));
+    int rc = drain_all();
+    if (rc) return rc;
+    if (persistent && prunning) { rc = persist_halt(); if (rc) return rc; }
+    shadow_blob = blob;
     return 0;
   }
 
@@ -1444,6 +1500,11 @@ int ccfd_engine_epoch_complete(void* eng, int64_t flip_count) {
 int ccfd_engine_set_blob(void* eng, const void* blob) {
   ApiLock lk(static_cast<Engine*>(eng));
   return static_cast<Engine*>(eng)->set_blob(blob);
+}
+
+int ccfd_engine_set_shadow(void* eng, const void* blob) {
+  ApiLock lk(static_cast<Engine*>(eng));
+  return static_cast<Engine*>(eng)->set_shadow(blob);
 }
 
 int64_t ccfd_engine_drain_flagged(void* eng, ccfd_flagged* out, int64_t max) {

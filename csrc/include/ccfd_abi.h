@@ -24,6 +24,13 @@ enum ccfd_counter_slot {
   CCFD_CNT_WIRE_STALE = 4,    // G32 / G20 rows whose bin stamp != the model's (proba NaN, standard route)
   CCFD_CNT_HIST_STD = 8,      // 14 amount buckets, standard route
   CCFD_CNT_HIST_FRAUD = 24,   // 14 amount buckets, fraud route
+  // Shadow (challenger) model scored beside the champion (score_shadow.hip); written only by
+  // the shadow kernels, so they stay zero while no shadow is set.
+  CCFD_CNT_SHADOW_ROWS = 40,        // valid rows the challenger scored
+  CCFD_CNT_SHADOW_FRAUD = 41,       // rows the challenger routes as fraud
+  CCFD_CNT_SHADOW_BOTH = 42,        // rows both models route as fraud
+  CCFD_CNT_SHADOW_PROBA_E6 = 43,    // sum(round(shadow proba_1 * 1e6)), rounded like slot 3
+  CCFD_CNT_SHADOW_ABSDIFF_E6 = 44,  // sum(round(|proba_1 - shadow proba_1| * 1e6))
   CCFD_CNT_SLOTS = 64
 };
 #define CCFD_N_AMOUNT_BUCKETS 14
@@ -141,6 +148,18 @@ int ccfd_score_launch(const ccfd_score_args* a, void* stream);
 // library has launched with before (a recycled allocation).
 void ccfd_forest_blob_changed(const void* blob);
 
+// Shadow scoring: a challenger MLP scored beside the champion in the same pass over the rows
+// (score_shadow.hip).  Both blobs are MLPs packed for W64 rows and route by
+// `proba >= threshold`; base.rules must be NULL.  The champion's outputs, counters, flag list
+// and completion record are those of ccfd_score_launch; the challenger adds the
+// CCFD_CNT_SHADOW_* counters and, when shadow_proba is non-NULL, its proba_1 per row.
+typedef struct ccfd_shadow_args {
+  ccfd_score_args base;
+  const void* shadow_blob;   // device memory, MLP W64 blob
+  float* shadow_proba;       // out [n] (device or host-mapped), may be NULL
+} ccfd_shadow_args;
+int ccfd_score_launch_shadow(const ccfd_shadow_args* a, void* stream);
+
 // ---------------------------------------------------------------------------
 // Persistent streaming kernel (exec_mode = 1): ONE long-running launch per engine; the
 // host publishes micro-batch descriptors into a ring in coherent pinned memory and bumps
@@ -198,6 +217,14 @@ typedef struct ccfd_persist_args {
 } ccfd_persist_args;
 
 int ccfd_persist_launch(const ccfd_persist_args* a, int grid, void* stream);
+
+// Persistent kernel with a shadow MLP: claimed W64 items of 2, 4 or 8 tiles per wave, MLP,
+// threshold route (no rules, no CCFD_ARG_PIPE_ITEMS); same host protocol as ccfd_persist_launch.
+typedef struct ccfd_persist_shadow_args {
+  ccfd_persist_args base;
+  const void* shadow_blob;   // device memory, MLP W64 blob
+} ccfd_persist_shadow_args;
+int ccfd_persist_launch_shadow(const ccfd_persist_shadow_args* a, int grid, void* stream);
 
 // ---------------------------------------------------------------------------
 // Host memory (pinned, device-mapped; used for partition logs and result rings)
@@ -327,6 +354,12 @@ int ccfd_engine_flip_epoch(void* eng, void* side_stream);
 int ccfd_engine_epoch_complete(void* eng, int64_t flip_count);
 // Hot swap: drain in-flight micro-batches, then score later ones with `blob` (same kind/shape).
 int ccfd_engine_set_blob(void* eng, const void* blob);
+// Shadow model (NULL = none): like set_blob, in-flight micro-batches drain and a resident
+// persistent kernel halts first; later submissions score the shadow beside the champion and
+// add the CCFD_CNT_SHADOW_* counters (no per-row shadow output).  Refused unless the engine
+// scores an MLP on W64 rows by threshold with claimed persistent items of 128 / 256 / 512 rows;
+// a launch-mode engine submits one launch per micro-batch (no coalescing) while one is set.
+int ccfd_engine_set_shadow(void* eng, const void* blob);
 // Drain up to `max` flagged records (fraud route) into `out`; returns count.
 int64_t ccfd_engine_drain_flagged(void* eng, ccfd_flagged* out, int64_t max);
 int64_t ccfd_engine_cursor(void* eng, int partition);

@@ -1,0 +1,346 @@
+// Shadow scoring: a challenger MLP scored beside the champion in the same pass over the rows.
+//
+// The streaming path is bound by the bytes a row costs on the link, not by model math, so the
+// way to tell what a hot swap would do to live traffic is to score the candidate on the very
+// rows the champion is scoring: both W64 weight blobs are staged in LDS once per workgroup and
+// every 16-row tile (or tile pair) held in registers goes through the MFMA chain twice, once
+// per LDS base.  The rows are read once; a second launch would read them twice.
+//
+// Both kernels run the champion's device functions (mlp_core.h) unchanged for the challenger
+// -- only the LDS base and the per-blob lane constants differ -- so rows scored with blob B as
+// the shadow carry the same bits as rows scored with B as the champion.
+//
+//   * score_shadow_kernel: one launch per micro-batch (plain launches, score_sync, the engine's
+//     exec_mode launch).  Champion epilogue as in wire_body.h (outputs, route, counters, amount
+//     histogram, staged flag list, completion record).
+//   * persist_shadow_kernel: the claimed-item path of score_persist.hip for W64 items of 2, 4
+//     or 8 tiles per wave, protocol helpers of persist_core.h unchanged: a workgroup waits only
+//     for the host and leaves on `stop`; workgroup 0 is the doorbell.
+//
+// The challenger adds five counters (CCFD_CNT_SHADOW_*), accumulated per wave, then per
+// workgroup in LDS, then one set of atomics per workgroup (launch) or item (persistent); the
+// launch kernel also stores its proba_1 per row when asked to.  MLP on W64 rows, threshold
+// route only: everything else is refused on the host.
+#include <string>
+#include <type_traits>
+
+#include "mlp_core.h"
+#include "persist_core.h"
+
+namespace ccfd {
+
+void set_error(const std::string& e);   // dispatch.hip
+
+namespace {
+
+constexpr int kShadowWaves = 4;          // waves per workgroup of the launch kernel
+// One tile pair per wave until the grid covers the chip: a CU reading host memory sustains only
+// a few GB/s, so a 4096-row micro-batch (256 tiles) is spread over 32 workgroups; past one
+// workgroup per CU the grid-stride loop takes over (each workgroup stages 56 KB of weights).
+constexpr int kShadowTilesPerWave = 2;
+constexpr int kShadowGridCap = 256;
+
+// Per-workgroup accumulators of the challenger's counters.
+struct ShadowLds {
+  unsigned int rows, fraud, both, pad;
+  unsigned long long psum_e6, absdiff_e6;
+};
+
+struct ShadowAcc {                       // per wave, in registers
+  unsigned fraud = 0, both = 0;
+  unsigned long long psum = 0, absdiff = 0;
+};
+
+__device__ __forceinline__ void shadow_init(ShadowLds& s) {
+  if (threadIdx.x == 64) { s.rows = 0; s.fraud = 0; s.both = 0; s.pad = 0; s.psum_e6 = 0; s.absdiff_e6 = 0; }
+}
+
+// One row's challenger bookkeeping, in the lane that owns the row's outputs.
+__device__ __forceinline__ void shadow_row(ShadowAcc& w, float p, float q) {
+  w.psum += (unsigned)(q * 1e6f + 0.5f);                 // the rounding of CCFD_CNT_PROBA_E6
+  w.absdiff += (unsigned)(fabsf(p - q) * 1e6f + 0.5f);
+}
+
+// Wave -> workgroup: `rows` = valid rows this wave scored (wave-uniform).
+__device__ __forceinline__ void shadow_wave_commit(ShadowLds& s, ShadowAcc& w, unsigned rows, int lane) {
+  w.psum = wave_sum_u64(w.psum);
+  w.absdiff = wave_sum_u64(w.absdiff);
+  if (lane == 0 && rows) {
+    atomicAdd(&s.rows, rows);
+    atomicAdd(&s.fraud, w.fraud);
+    atomicAdd(&s.both, w.both);
+    atomicAdd(&s.psum_e6, w.psum);
+    atomicAdd(&s.absdiff_e6, w.absdiff);
+  }
+}
+
+// Workgroup -> global, one thread, after a barrier that follows every wave's commit.
+__device__ __forceinline__ void shadow_flush(const ShadowLds& s, unsigned long long* cnt) {
+  if (cnt == nullptr || s.rows == 0) return;
+  atomicAdd(&cnt[CCFD_CNT_SHADOW_ROWS], (unsigned long long)s.rows);
+  atomicAdd(&cnt[CCFD_CNT_SHADOW_FRAUD], (unsigned long long)s.fraud);
+  atomicAdd(&cnt[CCFD_CNT_SHADOW_BOTH], (unsigned long long)s.both);
+  atomicAdd(&cnt[CCFD_CNT_SHADOW_PROBA_E6], s.psum_e6);
+  atomicAdd(&cnt[CCFD_CNT_SHADOW_ABSDIFF_E6], s.absdiff_e6);
+}
+
+// ---------------------------------------------------------------------------------------
+// Launch kernel.  Wave w of workgroup b streams tiles b * kWaves + w + k * tstride with a
+// two-tile prefetch ring: the steady-state loop scores the pair in the ring against both
+// blobs (mlp_tile_w64_x2: one LDS weight read feeds two MFMAs) and refills both slots before
+// the epilogue; at most one tile is left for the tail (mlp_tile_w64).  Loads are branch-free
+// (rows clamped into the batch; clamped rows are never scored), as in wire_body.h.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64 * kShadowWaves) void score_shadow_kernel(ccfd_shadow_args sa) {
+  constexpr int kWaves = kShadowWaves;
+  __shared__ __attribute__((aligned(16))) char lds[2][kMlpBlobWire];
+  __shared__ EpilogueLds epi;
+  __shared__ ShadowLds sh;
+  __shared__ unsigned flbuf[kWaves][128];
+  const ccfd_score_args& a = sa.base;
+  const int blk = blockIdx.x, nblk = gridDim.x;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 4, c = lane & 15;
+  stamp_start(a, blk);
+  const int n = a.n;
+  const int ntiles = (n + kTileRows - 1) / kTileRows;
+  const int tstride = nblk * kWaves;
+  int tile = blk * kWaves + wave;
+  const unsigned char* xw = reinterpret_cast<const unsigned char*>(a.x) + 16 * g;
+  auto issue = [&](int t, WireRegs& r) __attribute__((always_inline)) {
+    const int row = min(t * kTileRows + c, n - 1);
+    r.v = ld_g16(xw + (size_t)row * CCFD_WIRE_ROW_BYTES);
+  };
+  // the first pair's (possibly PCIe) fetch overlaps the staging of the two blobs
+  WireRegs r0, r1;
+  issue(tile, r0);
+  issue(tile + tstride, r1);
+  mlp_stage(a.blob, lds[0], tid, 64 * kWaves, kMlpBlobWire);
+  mlp_stage(sa.shadow_blob, lds[1], tid, 64 * kWaves, kMlpBlobWire);
+  epi_init(epi);
+  shadow_init(sh);
+  __syncthreads();
+  const MlpWireLane LA = mlp_wire_lane(lds[0]);
+  const MlpWireLane LB = mlp_wire_lane(lds[1]);
+
+  const float thr = a.threshold;
+  FlagStage fls{flbuf[wave], 0u};
+  unsigned fraud = 0, rows = 0;
+  unsigned long long psum = 0;
+  ShadowAcc sw;
+  HistLanes hl;
+  hist_lanes_init(hl, g);
+  // p: champion, q: challenger proba_1 of row c of tile t (identical in the 4 lane groups)
+  auto finish = [&](float p, float q, float amount, int t) __attribute__((always_inline)) {
+    const int row = t * kTileRows + c;
+    const bool valid = row < n;
+    const bool fr = valid && (p >= thr);
+    const bool sf = valid && (q >= thr);
+    if (valid && g == 0) {
+      if (a.proba) st_g(a.proba + row, p);
+      if (a.route) st_g(a.route + row, (uint8_t)(fr ? 1 : 0));
+      psum += (unsigned)(p * 1e6f + 0.5f);
+      if (sa.shadow_proba) st_g(sa.shadow_proba + row, q);
+      shadow_row(sw, p, q);
+    }
+    const unsigned long long frm = __ballot(fr && g == 3);     // same rows as the g == 0 lanes
+    fraud += __popcll(frm);
+    rows += (unsigned)min(kTileRows, n - t * kTileRows);
+    sw.fraud += __popcll(__ballot(sf && g == 3));
+    sw.both += __popcll(__ballot(sf && fr && g == 3));
+    const float am_g3 = (valid && g == 3) ? amount : -__builtin_inff();
+    hist_lanes_add(hl, __shfl(am_g3, 48 + c));
+    if (frm) {                                                   // rare: fraud rows' buckets
+      if (fr && g == 3) atomicAdd(&epi.hist[kNB + amount_bucket_fast(amount)], 1u);
+      flag_push(a, fls, frm, fr && g == 3, row, lane);
+    }
+  };
+  // steady state: both tiles of the pair exist
+  const int full_end = ntiles - tstride;
+  while (tile < full_end) {
+    const float am0 = __uint_as_float(r0.v.w), am1 = __uint_as_float(r1.v.w);
+    float p0, p1, q0, q1;
+    mlp_tile_w64_x2(lds[0], LA, r0, r1, g, lane, p0, p1);
+    mlp_tile_w64_x2(lds[1], LB, r0, r1, g, lane, q0, q1);
+    issue(tile + 2 * tstride, r0);
+    issue(tile + 3 * tstride, r1);
+    finish(p0, q0, am0, tile);
+    finish(p1, q1, am1, tile + tstride);
+    tile += 2 * tstride;
+  }
+  // tail: at most one tile left, already in r0
+  if (tile < ntiles) {
+    const float p = mlp_tile_w64(lds[0], LA, r0, g, lane);
+    const float q = mlp_tile_w64(lds[1], LB, r0, g, lane);
+    finish(p, q, __uint_as_float(r0.v.w), tile);
+  }
+  if (a.flag_idx != nullptr) flag_flush(a, fls, lane);
+  psum = wave_sum_u64(psum);
+  hist_lanes_commit(epi, hl, g, c);
+  if (lane == 0) {
+    atomicAdd(&epi.fraud, fraud);
+    atomicAdd(&epi.rows, rows);
+    atomicAdd(&epi.psum_e6, psum);
+  }
+  shadow_wave_commit(sh, sw, rows, lane);
+  epi_flush_ballot(epi, a.counters);                    // barrier first, then the champion's atomics
+  if (tid == 2 * kNB + 1) shadow_flush(sh, a.counters);
+  signal_done(a, (unsigned)nblk);
+}
+
+// ---------------------------------------------------------------------------------------
+// Persistent kernel: persist_kernel's full_item path (score_persist.hip) with both blobs
+// staged once per resident workgroup.  Every tile of the claimed item is in flight at once
+// and scored in pairs, first against the champion, then against the challenger.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void persist_shadow_kernel(ccfd_persist_shadow_args sa) {
+  __shared__ __attribute__((aligned(16))) char sblob[2][kMlpBlobWire];
+  __shared__ EpilogueLds epi;
+  __shared__ ShadowLds sh;
+  __shared__ ccfd_persist_desc sdesc;
+  __shared__ unsigned long long s_item;
+  __shared__ int s_cmd;
+  const ccfd_persist_args& a = sa.base;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 4, c = lane & 15;
+  const int C = a.items_per_batch;
+
+  mlp_stage(a.blob, sblob[0], tid, 256, kMlpBlobWire);
+  mlp_stage(sa.shadow_blob, sblob[1], tid, 256, kMlpBlobWire);
+  epi_init(epi);
+  shadow_init(sh);
+  __syncthreads();
+  const MlpWireLane LA = mlp_wire_lane(sblob[0]);
+  const MlpWireLane LB = mlp_wire_lane(sblob[1]);
+  unsigned long long posted_cache = 0;     // thread 0 only
+
+  // Workgroup 0 is the DOORBELL (persist_core.h): its first wave alone polls host memory.
+  if (blockIdx.x == 0) {
+    if (wave == 0) persist_doorbell(a, lane);
+    return;                                              // no barrier is ever used by WG 0
+  }
+
+  for (;;) {
+    if (tid == 0) persist_claim(a, C, posted_cache, sdesc, s_item, s_cmd);
+    __syncthreads();
+    if (s_cmd) break;
+
+    const unsigned long long item = s_item;
+    const ccfd_persist_desc dsc = sdesc;
+    const int chunk = (int)(item % (unsigned long long)C);
+    const int slot = (int)(dsc.seq % (unsigned long long)a.ring);
+    const int n = dsc.n;
+    const int kTilesPerWave = a.tiles_per_wave;
+    const int tile0 = chunk * (4 * kTilesPerWave) + wave;      // wave w: tiles tile0 + 4k
+    if (chunk == 0 && tid == 0)                                // K7: micro-batch start (item 0 claimed first)
+      __hip_atomic_store(&a.dev->tstart[slot], wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned char* xw = reinterpret_cast<const unsigned char*>(dsc.x);
+    unsigned nf_w = 0, nv_w = 0;
+    unsigned long long ps_w = 0;
+    ShadowAcc sw;
+    // per-tile epilogue: the champion's as in persist_kernel, then the challenger's counters
+    auto finish = [&](float p, float q, float amount, int tile) __attribute__((always_inline)) {
+      const int row = tile * kTileRows + c;
+      const bool valid = row < n;
+      const bool fr = valid && (p >= a.threshold);
+      const bool sf = valid && (q >= a.threshold);
+      if (valid && g == 0) {
+        if (dsc.proba) st_g(dsc.proba + row, p);
+        if (dsc.route) st_g(dsc.route + row, (uint8_t)(fr ? 1 : 0));
+        ps_w += (unsigned long long)(p * 1e6f + 0.5f);
+        shadow_row(sw, p, q);
+      }
+      const unsigned long long m = __ballot(fr && g == 0);
+      nf_w += __popcll(m);
+      nv_w += __popcll(__ballot(valid && g == 0));
+      sw.fraud += __popcll(__ballot(sf && g == 0));
+      sw.both += __popcll(__ballot(sf && fr && g == 0));
+      if (valid && g == 3) atomicAdd(&epi.hist[(fr ? kNB : 0) + amount_bucket(amount)], 1u);
+      persist_emit_flagged(a, dsc, slot, m, fr && g == 0, row, lane);
+    };
+    auto full_item = [&](auto kT) __attribute__((always_inline)) {
+      constexpr int T = decltype(kT)::value;
+      WireRegs r[T];
+#pragma unroll
+      for (int k = 0; k < T; ++k) wire_issue(xw, n, tile0 + 4 * k, c, g, r[k]);
+#pragma unroll
+      for (int k = 0; k < T; k += 2) {
+        const int ta = tile0 + 4 * k;
+        if (ta * kTileRows >= n) break;                    // wave-uniform
+        float pa, pb, qa, qb;
+        mlp_tile_w64_x2(sblob[0], LA, r[k], r[k + 1], g, lane, pa, pb);
+        mlp_tile_w64_x2(sblob[1], LB, r[k], r[k + 1], g, lane, qa, qb);
+        finish(pa, qa, __uint_as_float(r[k].v.w), ta);
+        finish(pb, qb, __uint_as_float(r[k + 1].v.w), ta + 4);   // rows >= n: no-op epilogue
+      }
+    };
+    // the host launches this kernel with 2, 4 or 8 tiles per wave only
+    if (kTilesPerWave == 2) {
+      full_item(std::integral_constant<int, 2>{});
+    } else if (kTilesPerWave == 4) {
+      full_item(std::integral_constant<int, 4>{});
+    } else {
+      full_item(std::integral_constant<int, 8>{});
+    }
+    ps_w = wave_sum_u64(ps_w);
+    if (lane == 0 && nv_w) {
+      atomicAdd(&epi.fraud, nf_w);
+      atomicAdd(&epi.rows, nv_w);
+      atomicAdd(&epi.psum_e6, ps_w);
+    }
+    shadow_wave_commit(sh, sw, nv_w, lane);
+    // the item's challenger counters, then LDS reset for the next item: persist_item_done's
+    // barriers and its vmcnt(0) drain order both before the item's ticket and the next claim
+    __syncthreads();
+    if (tid == 96) {
+      shadow_flush(sh, a.counters[dsc.epoch & 1]);
+      sh.rows = 0; sh.fraud = 0; sh.both = 0; sh.psum_e6 = 0; sh.absdiff_e6 = 0;
+    }
+    persist_item_done(a, epi, dsc, slot, C, tid);
+  }
+}
+
+}  // namespace
+
+}  // namespace ccfd
+
+extern "C" int ccfd_score_launch_shadow(const ccfd_shadow_args* sa, void* stream) {
+  using namespace ccfd;
+  if (sa == nullptr || sa->base.blob == nullptr || sa->base.x == nullptr || sa->shadow_blob == nullptr) {
+    set_error("shadow launch: null argument");
+    return -1;
+  }
+  const ccfd_score_args& a = sa->base;
+  if (a.n < 0) { set_error("n < 0"); return -1; }
+  if (a.model != CCFD_MODEL_MLP) { set_error("shadow launch: champion and shadow must both be MLPs (model kind refused)"); return -3; }
+  if (!(a.flags & CCFD_ARG_WIRE_W64) || (a.flags & (CCFD_ARG_WIRE_G32 | CCFD_ARG_WIRE_G20))) {
+    set_error("shadow launch: W64 rows only (f32 / G32 / G20 rows refused)");
+    return -3;
+  }
+  if (a.rules != nullptr) { set_error("shadow launch: threshold route only (routing rules refused)"); return -3; }
+  if (reinterpret_cast<uintptr_t>(a.x) & 15) { set_error("W64 rows must be 16-byte aligned"); return -3; }
+  if (a.n == 0) return 0;
+  const int ntiles = (a.n + kTileRows - 1) / kTileRows;
+  const int per_wg = kShadowWaves * kShadowTilesPerWave;
+  int grid = (ntiles + per_wg - 1) / per_wg;
+  grid = grid > kShadowGridCap ? kShadowGridCap : grid;
+  hipLaunchKernelGGL(score_shadow_kernel, dim3(grid), dim3(64 * kShadowWaves), 0, reinterpret_cast<hipStream_t>(stream),
+                     *sa);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) { set_error(std::string("kernel launch failed: ") + hipGetErrorString(e)); return -5; }
+  return 0;
+}
+
+extern "C" int ccfd_persist_launch_shadow(const ccfd_persist_shadow_args* sa, int grid, void* stream) {
+  using namespace ccfd;
+  if (!sa || !sa->base.ctl || !sa->base.desc || !sa->base.dev || !sa->base.blob || !sa->shadow_blob) return -1;
+  const ccfd_persist_args& a = sa->base;
+  if (a.ring <= 0 || a.ring > CCFD_PERSIST_MAX_RING || a.items_per_batch <= 0 || grid < 2) return -2;
+  if (a.model != CCFD_MODEL_MLP || !(a.flags & CCFD_ARG_WIRE_W64) || (a.flags & CCFD_ARG_PIPE_ITEMS) || a.rules) return -3;
+  if (a.tiles_per_wave != 2 && a.tiles_per_wave != 4 && a.tiles_per_wave != 8) return -2;
+  hipLaunchKernelGGL(persist_shadow_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *sa);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
