@@ -59,6 +59,22 @@ class PersistShadowArgs(C.Structure):    # ccfd_persist_shadow_args
     _fields_ = [("base", PersistArgs), ("shadow_blob", C.c_void_p)]
 
 
+GBDT_HIST_MAX_LEVEL, GBDT_HIST_MAX_BINS, GBDT_MAX_SPLITS = 7, 64, 8      # ccfd_abi.h CCFD_GBDT_*
+
+
+class GbdtHistArgs(C.Structure):         # ccfd_gbdt_hist_args
+    _fields_ = [("rows", C.c_void_p), ("grad", C.c_void_p), ("hess", C.c_void_p), ("G", C.c_void_p),
+                ("H", C.c_void_p), ("n", C.c_int64), ("n_bins", C.c_int32), ("level", C.c_int32),
+                ("split_feat", C.c_int32 * GBDT_MAX_SPLITS), ("split_bin", C.c_int32 * GBDT_MAX_SPLITS)]
+
+
+class GbdtUpdateArgs(C.Structure):       # ccfd_gbdt_update_args
+    _fields_ = [("rows", C.c_void_p), ("leaf_val", C.c_void_p), ("raw", C.c_void_p), ("y", C.c_void_p),
+                ("grad", C.c_void_p), ("hess", C.c_void_p), ("n", C.c_int64), ("depth", C.c_int32),
+                ("pad", C.c_int32), ("split_feat", C.c_int32 * GBDT_MAX_SPLITS),
+                ("split_bin", C.c_int32 * GBDT_MAX_SPLITS)]
+
+
 class EngineConfig(C.Structure):
     _fields_ = [("device", C.c_int32), ("model", C.c_int32), ("blob", C.c_void_p),
                 ("gbdt_trees", C.c_int32), ("gbdt_depth", C.c_int32), ("threshold", C.c_float),
@@ -130,6 +146,10 @@ def lib() -> C.CDLL:
         L.ccfd_score_launch_shadow.restype = C.c_int
         L.ccfd_persist_launch_shadow.argtypes = [C.POINTER(PersistShadowArgs), C.c_int, C.c_void_p]
         L.ccfd_persist_launch_shadow.restype = C.c_int
+        L.ccfd_gbdt_hist_launch.argtypes = [C.POINTER(GbdtHistArgs), C.c_void_p]
+        L.ccfd_gbdt_hist_launch.restype = C.c_int
+        L.ccfd_gbdt_update_launch.argtypes = [C.POINTER(GbdtUpdateArgs), C.c_void_p]
+        L.ccfd_gbdt_update_launch.restype = C.c_int
         L.ccfd_forest_blob_changed.argtypes = [C.c_void_p]
         L.ccfd_forest_blob_changed.restype = None
         L.ccfd_host_alloc.argtypes = [C.c_size_t]

@@ -12,8 +12,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from ._lib import (ARG_WIRE_G20, ARG_WIRE_G32, ARG_WIRE_W64, BIN_FORMATS, MODEL_IDS, N_COUNTER_SLOTS, ScoreArgs,
-                   ShadowArgs, check, lib)
+from ._lib import (ARG_WIRE_G20, ARG_WIRE_G32, ARG_WIRE_W64, BIN_FORMATS, GBDT_MAX_SPLITS, MODEL_IDS, N_COUNTER_SLOTS,
+                   GbdtHistArgs, GbdtUpdateArgs, ScoreArgs, ShadowArgs, check, lib)
 
 N_FEATURES = 30
 ROW_BYTES = {"f32": 4 * N_FEATURES, "w64": 64, "g32": 32, "g20": 20}
@@ -184,3 +184,89 @@ def score(dm: DeviceModel, x: torch.Tensor, threshold: float = 0.5,
         return proba, route, shadow_proba
     check(lib().ccfd_score_launch(C.byref(a), C.c_void_p(s.cuda_stream)), "ccfd_score_launch")
     return proba, route
+
+
+# ---------------------------------------------------------------------------- GBDT training
+def _g32_rows(rows: torch.Tensor) -> int:
+    if not rows.is_cuda or rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != ROW_BYTES["g32"] or \
+            not rows.is_contiguous():
+        raise ValueError("rows must be contiguous CUDA G32 rows ([n,32] u8)")
+    return rows.shape[0]
+
+
+def _f32_vec(t: torch.Tensor, n: int, name: str, like: torch.Tensor) -> None:
+    if not t.is_cuda or t.device != like.device or t.dtype != torch.float32 or t.dim() != 1 or t.shape[0] != n or \
+            not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous CUDA float32 tensor of shape [{n}] on the rows' device")
+
+
+def _set_splits(a, splits) -> int:
+    splits = [(int(f), int(b)) for f, b in splits]
+    if len(splits) > GBDT_MAX_SPLITS:
+        raise ValueError(f"at most {GBDT_MAX_SPLITS} splits (got {len(splits)})")
+    for k, (f, b) in enumerate(splits):
+        a.split_feat[k], a.split_bin[k] = f, b
+    return len(splits)
+
+
+def gbdt_histogram(rows: torch.Tensor, grad: torch.Tensor, hess: torch.Tensor, n_bins: int, splits=(),
+                   out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None,
+                   stream: Optional[torch.cuda.Stream] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One level's gradient / hessian histograms of an oblivious tree over G32 rows
+    (csrc/kernels/train_hist.hip): with ``d = len(splits)`` pairs ``(feature, bin)`` chosen so far,
+    ``leaf(i) = sum_k (rows[i, feature_k] > bin_k) << k`` and
+    ``G[leaf(i), f, rows[i, f]] += grad[i]`` for every row and feature (``H`` with ``hess``).
+    Returns ``(G, H)``, float32 ``[2^d, 30, n_bins]``, overwritten (``out=`` reuses two such
+    tensors).  Supported: d <= 7, 2 <= n_bins <= 64, n >= 1; anything else is refused by the
+    library (``RuntimeError`` with its message).  Bytes 30 / 31 of a row are ignored; a bin byte
+    >= n_bins is skipped.  The sums are f32 in no fixed order, so the last bits can differ from
+    run to run (as with ``scatter_add_``)."""
+    n = _g32_rows(rows)
+    _f32_vec(grad, n, "grad", rows)
+    _f32_vec(hess, n, "hess", rows)
+    a = GbdtHistArgs()
+    d = _set_splits(a, splits)
+    shape = (1 << d, N_FEATURES, int(n_bins))
+    if out is None:
+        out = (torch.empty(shape, dtype=torch.float32, device=rows.device),
+               torch.empty(shape, dtype=torch.float32, device=rows.device))
+    G, H = out
+    for name, t in (("G", G), ("H", H)):
+        if not t.is_cuda or t.device != rows.device or t.dtype != torch.float32 or tuple(t.shape) != shape or \
+                not t.is_contiguous():
+            raise ValueError(f"out {name} must be a contiguous CUDA float32 tensor of shape {list(shape)}")
+    a.rows, a.grad, a.hess = rows.data_ptr(), grad.data_ptr(), hess.data_ptr()
+    a.G, a.H = G.data_ptr(), H.data_ptr()
+    a.n, a.n_bins, a.level = n, int(n_bins), d
+    s = stream if stream is not None else torch.cuda.current_stream(rows.device)
+    check(lib().ccfd_gbdt_hist_launch(C.byref(a), C.c_void_p(s.cuda_stream)), "ccfd_gbdt_hist_launch")
+    return G, H
+
+
+def gbdt_apply_tree(rows: torch.Tensor, raw: torch.Tensor, leaf_val: torch.Tensor, splits,
+                    y: Optional[torch.Tensor] = None, grad: Optional[torch.Tensor] = None,
+                    hess: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None):
+    """Close a tree of ``depth = len(splits)`` (1..8): ``raw[i] += leaf_val[leaf(i)]`` in place,
+    with ``leaf(i)`` as in ``gbdt_histogram``.  With labels ``y`` it also writes the next tree's
+    logloss gradients ``grad = sigmoid(raw) - y`` and ``hess = max(p (1 - p), 1e-6)`` (allocated
+    unless given) and returns ``(raw, grad, hess)``; without ``y`` it returns ``(raw, None, None)``."""
+    n = _g32_rows(rows)
+    _f32_vec(raw, n, "raw", rows)
+    a = GbdtUpdateArgs()
+    depth = _set_splits(a, splits)
+    _f32_vec(leaf_val, 1 << depth, "leaf_val", rows)
+    if y is None:
+        if grad is not None or hess is not None:
+            raise ValueError("grad= / hess= need y=")
+    else:
+        _f32_vec(y, n, "y", rows)
+        grad = torch.empty_like(raw) if grad is None else grad
+        hess = torch.empty_like(raw) if hess is None else hess
+        _f32_vec(grad, n, "grad", rows)
+        _f32_vec(hess, n, "hess", rows)
+        a.y, a.grad, a.hess = y.data_ptr(), grad.data_ptr(), hess.data_ptr()
+    a.rows, a.leaf_val, a.raw = rows.data_ptr(), leaf_val.data_ptr(), raw.data_ptr()
+    a.n, a.depth = n, depth
+    s = stream if stream is not None else torch.cuda.current_stream(rows.device)
+    check(lib().ccfd_gbdt_update_launch(C.byref(a), C.c_void_p(s.cuda_stream)), "ccfd_gbdt_update_launch")
+    return raw, grad, hess

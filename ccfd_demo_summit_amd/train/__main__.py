@@ -62,6 +62,9 @@ def main(argv=None) -> int:
     ap.add_argument("--max-borders", type=int, default=31,
                     help="GBDT: split candidates per feature (<= 31 keeps every trained ensemble on the "
                          "20-byte G20 row format; <= 255 for G32)")
+    ap.add_argument("--hist", default="torch", choices=["torch", "hip", "auto"],
+                    help="GBDT: histogram backend -- torch scatter_add (default), the HIP histogram kernel over "
+                         "G32 rows (CUDA device, <= 64 bins), or auto (hip when it can)")
     ap.add_argument("--metrics-port", type=int, default=0,
                     help="serve the trainer's /metrics (the SparkMetrics dashboard series) on this port "
                          "(+ rank) while training; 0 = off")
@@ -121,7 +124,7 @@ def main(argv=None) -> int:
         dev = f"cuda:{torch.cuda.current_device()}"
     if a.model == "gbdt":
         model, info = train_oblivious_gbdt(X[tr], y[tr], n_trees=a.trees, depth=a.depth, device=dev,
-                                           n_bins=a.max_borders + 1)
+                                           n_bins=a.max_borders + 1, hist=a.hist)
     else:
         cfg = TrainConfig(epochs=a.epochs, batch=a.batch, device=dev, seed=a.seed, metrics=tm)
         model, info = (train_mlp if a.model == "mlp" else train_logistic)(X[tr], y[tr], cfg)

@@ -7,7 +7,8 @@ deploy/frauddetection_cr.yaml:7-53).
   ``MLPModel`` containers the HIP kernels consume, so a trained model is packed and
   hot-swapped exactly like a random-init one.
 * ``train_oblivious_gbdt``: gradient-boosted oblivious trees (logloss, second-order
-  leaves, quantile-binned splits) with histograms built by ``scatter_add`` on the GPU.
+  leaves, quantile-binned splits) with histograms built by ``scatter_add`` on the GPU, or
+  (``hist="hip"``) by the HIP histogram kernel over G32 rows (csrc/kernels/train_hist.hip).
 """
 from __future__ import annotations
 
@@ -196,9 +197,84 @@ def _quantile_borders(X: np.ndarray, n_bins: int) -> np.ndarray:
     return np.quantile(X, qs, axis=0).T.astype(np.float32)        # [F, n_bins-1]
 
 
+HIP_HIST_MAX_BINS = 64      # csrc/include/ccfd_abi.h CCFD_GBDT_HIST_MAX_BINS
+HIP_HIST_MAX_DEPTH = 8      # CCFD_GBDT_MAX_SPLITS (the last histogram level is depth - 1 <= 7)
+HIST_BACKENDS = ("torch", "hip", "auto")
+
+
+def _hip_hist_refusal(dev: torch.device, n_bins: int, depth: int, n_features: int) -> Optional[str]:
+    """Why the HIP histogram path cannot train this shape (None: it can)."""
+    if n_bins > HIP_HIST_MAX_BINS:
+        return f"n_bins = {n_bins} exceeds its limit of {HIP_HIST_MAX_BINS} bins per feature"
+    if n_bins < 2:
+        return f"n_bins = {n_bins}: it needs at least 2 bins per feature"
+    if not 1 <= depth <= HIP_HIST_MAX_DEPTH:
+        return f"depth = {depth} is outside its range 1..{HIP_HIST_MAX_DEPTH}"
+    if n_features != 30:
+        return f"{n_features} features: G32 rows hold exactly 30"
+    if dev.type != "cuda":
+        return f"device {str(dev)!r}: it needs a CUDA device"
+    return None
+
+
+def _encode_training_rows(X: np.ndarray, borders: np.ndarray) -> np.ndarray:
+    """X [n, 30] f32 -> G32 rows [n, 32] u8 against ``borders`` [30, B-1] as a bin table
+    (native encoder, csrc/engine/ingest.cpp): byte j = #borders_j < x_j, the trainer's
+    ``searchsorted(..., "left")``, except that NaN goes to bin 0."""
+    import os
+    from ..ops._lib import lib
+    X = np.ascontiguousarray(X, np.float32)
+    n, F = X.shape
+    flat = np.ascontiguousarray(borders, np.float32).reshape(-1)
+    offsets = (np.arange(F + 1, dtype=np.int32) * np.int32(borders.shape[1])).astype(np.int32)
+    rows = np.empty((n, 32), np.uint8)
+    threads = max(1, min(16, os.cpu_count() or 1, (n + 65535) // 65536))
+    if lib().ccfd_encode_bins_mt(X.ctypes.data, n, F, flat.ctypes.data, offsets.ctypes.data, 1, 0,
+                                 rows.ctypes.data, None, threads) != n:
+        raise RuntimeError("ccfd_encode_bins_mt failed")
+    return rows
+
+
+def _boost_hip(rows: torch.Tensor, yt: torch.Tensor, raw: torch.Tensor, borders: np.ndarray, feat: np.ndarray,
+               thr: np.ndarray, leaves: np.ndarray, l2: float, learning_rate: float, allreduce) -> None:
+    """The boosting loop of ``train_oblivious_gbdt(hist="hip")``: fills feat / thr / leaves and
+    advances ``raw`` in place.  Per level one histogram launch over the G32 ``rows``, then the
+    all-reduce and the gain scan of the torch path; per tree one update launch."""
+    from ..ops.kernels import gbdt_apply_tree, gbdt_histogram
+    n_trees, depth = feat.shape
+    B = borders.shape[1] + 1
+    prob = torch.sigmoid(raw)
+    grad = prob - yt
+    hess = (prob * (1 - prob)).clamp_min(1e-6)
+    for t in range(n_trees):
+        splits = []
+        for d in range(depth):
+            G, H = gbdt_histogram(rows, grad, hess, B, splits)         # [2^d, F, B], overwritten
+            G, H = allreduce(G), allreduce(H)
+            Gl = G.cumsum(-1)[..., :-1]                                # split after bin b: left = bins <= b
+            Hl = H.cumsum(-1)[..., :-1]
+            Gt = G.sum(-1, keepdim=True)
+            Ht = H.sum(-1, keepdim=True)
+            Gr, Hr = Gt - Gl, Ht - Hl
+            gain = (Gl ** 2 / (Hl + l2) + Gr ** 2 / (Hr + l2) - Gt ** 2 / (Ht + l2)).sum(0)   # [F, B-1]
+            best = int(torch.argmax(gain))
+            f, b = divmod(best, B - 1)
+            feat[t, d] = f
+            thr[t, d] = borders[f, b]
+            splits.append((f, b))
+        # the last split sends leaf l's rows left (stay l) or right (l + 2^(depth-1)): its partial
+        # sums ARE the 2^depth leaf totals, already all-reduced
+        Gs = torch.cat([G[:, f, :b + 1].sum(-1), G[:, f, b + 1:].sum(-1)])
+        Hs = torch.cat([H[:, f, :b + 1].sum(-1), H[:, f, b + 1:].sum(-1)])
+        vals = (-learning_rate * Gs / (Hs + l2)).contiguous()
+        leaves[t] = vals.cpu().numpy()
+        gbdt_apply_tree(rows, raw, vals, splits, y=yt, grad=grad, hess=hess)
+
+
 def train_oblivious_gbdt(X: np.ndarray, y: np.ndarray, n_trees: int = 100, depth: int = 6,
                          learning_rate: float = 0.1, n_bins: int = 32, l2: float = 1.0,
-                         device: str = "auto", borders: Optional[np.ndarray] = None) -> Tuple[ObliviousGBDT, Dict]:
+                         device: str = "auto", borders: Optional[np.ndarray] = None,
+                         hist: str = "torch") -> Tuple[ObliviousGBDT, Dict]:
     """Level-wise oblivious boosting on logloss.  At each level one (feature, border) is
     chosen for ALL current leaves (maximum summed second-order gain).
 
@@ -209,7 +285,28 @@ def train_oblivious_gbdt(X: np.ndarray, y: np.ndarray, n_trees: int = 100, depth
     the leaf sums and the base-rate statistics are all-reduced (SUM), so every rank grows
     the same trees -- the ones a single process would grow on the union of the shards, up to
     float summation order.  ``borders`` [F, n_bins-1]: use these split candidates instead of
-    quantiles of X."""
+    quantiles of X.
+
+    ``hist`` picks how the histograms are built; ``info["hist"]`` reports the path used.
+
+    * ``"torch"`` (default): an int64 bin matrix and two ``scatter_add_`` per level.
+    * ``"hip"``: X is encoded once into G32 rows (32 B a row, the borders as the bin table),
+      each level is one launch of the LDS-privatised histogram kernel
+      (``ops.kernels.gbdt_histogram``, csrc/kernels/train_hist.hip), the leaf sums are read off
+      the last level's histogram, and one update launch per tree (``ops.kernels.gbdt_apply_tree``)
+      advances the raw scores and writes the next gradients / hessians.  No per-row leaf array
+      and no int64 matrix exist on the device.  The all-reduce of G / H and the gain scan are
+      the torch path's.  It needs a CUDA device, ``n_bins <= 64`` and ``depth <= 8``; otherwise
+      ``ValueError`` names the limit.
+    * ``"auto"``: ``"hip"`` when those conditions hold, else ``"torch"``.
+
+    Both paths sum in f32 in no fixed order (float atomics), so histograms -- and with them a
+    near-tied split choice -- can differ in the last bits between the paths and from run to
+    run.  They bin identically except for NaN: the G32 encoder sends NaN to bin 0, which is
+    how the scorers treat it (``x > thr`` is false), while the torch path's ``searchsorted``
+    sends it to the last bin."""
+    if hist not in HIST_BACKENDS:
+        raise ValueError(f"hist must be one of {HIST_BACKENDS}, got {hist!r}")
     dev = _device(device)
     rank, world = _ddp_ctx()
 
@@ -220,6 +317,12 @@ def train_oblivious_gbdt(X: np.ndarray, y: np.ndarray, n_trees: int = 100, depth
         return t
 
     X = np.asarray(X, np.float32)
+    use_hip = False
+    if hist != "torch":
+        why = _hip_hist_refusal(dev, n_bins if borders is None else np.shape(borders)[1] + 1, depth, X.shape[1])
+        if why is not None and hist == "hip":
+            raise ValueError(f"hist='hip': {why}")
+        use_hip = why is None
     if borders is None:
         borders = _quantile_borders(X, n_bins)                      # [F, B-1]
     if world > 1:
@@ -233,10 +336,13 @@ def train_oblivious_gbdt(X: np.ndarray, y: np.ndarray, n_trees: int = 100, depth
         dist.broadcast(bt0, 0)
         borders = bt0.cpu().numpy()
     # bin index of every value: number of borders strictly below it -> x > border[b] iff bin > b
-    bins = np.empty((n, F), np.int64)
-    for f in range(F):
-        bins[:, f] = np.searchsorted(borders[f], X[:, f], side="left")
-    bt = torch.from_numpy(bins).to(dev)
+    if use_hip:
+        rows = torch.from_numpy(_encode_training_rows(X, borders)).to(dev)      # [n, 32] u8
+    else:
+        bins = np.empty((n, F), np.int64)
+        for f in range(F):
+            bins[:, f] = np.searchsorted(borders[f], X[:, f], side="left")
+        bt = torch.from_numpy(bins).to(dev)
     yt = torch.from_numpy(y.astype(np.float32)).to(dev)
     stats = allreduce(torch.tensor([float(y.sum()), float(n)], dtype=torch.float64, device=dev))
     p0 = float(np.clip(float(stats[0]) / max(float(stats[1]), 1.0), 1e-6, 1 - 1e-6))
@@ -247,7 +353,11 @@ def train_oblivious_gbdt(X: np.ndarray, y: np.ndarray, n_trees: int = 100, depth
     leaves = np.zeros((n_trees, 1 << depth), np.float32)
     B = n_bins
     fidx = torch.arange(F, device=dev)
-    for t in range(n_trees):
+    import time as _time
+    t_boost = _time.perf_counter()
+    if use_hip:
+        _boost_hip(rows, yt, raw, borders, feat, thr, leaves, l2, learning_rate, allreduce)
+    for t in range(0 if use_hip else n_trees):                         # hist="torch"
         prob = torch.sigmoid(raw)
         grad = prob - yt
         hess = (prob * (1 - prob)).clamp_min(1e-6)
@@ -279,7 +389,9 @@ def train_oblivious_gbdt(X: np.ndarray, y: np.ndarray, n_trees: int = 100, depth
     with torch.no_grad():
         ll_sum = torch.nn.functional.binary_cross_entropy_with_logits(raw, yt, reduction="sum").double()
         ll = float(allreduce(ll_sum.reshape(1))[0]) / max(float(stats[1]), 1.0)
-    return model, {"train_logloss": ll, "trees": n_trees, "depth": depth, "world": world}
+    return model, {"train_logloss": ll, "trees": n_trees, "depth": depth, "world": world,
+                   "hist": "hip" if use_hip else "torch",
+                   "seconds_boost": _time.perf_counter() - t_boost}       # the tree loop, binning excluded
 
 
 def evaluate(model, X: np.ndarray, y: np.ndarray) -> Dict[str, float]:

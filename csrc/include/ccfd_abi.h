@@ -161,6 +161,50 @@ typedef struct ccfd_shadow_args {
 int ccfd_score_launch_shadow(const ccfd_shadow_args* a, void* stream);
 
 // ---------------------------------------------------------------------------
+// Oblivious-GBDT training on G32 rows (train_hist.hip; train/trainer.py hist="hip").  A row's
+// bytes 0..29 are its training bins (bin = #borders < x); bytes 30 / 31 are ignored.  The leaf
+// of row i under the first d chosen splits is
+//   leaf(i) = sum_{k<d} (rows[i][split_feat[k]] > split_bin[k]) << k
+// so neither launch needs a per-row leaf array.  Both are plain grid launches on `stream`.
+#define CCFD_GBDT_HIST_MAX_LEVEL 7
+#define CCFD_GBDT_HIST_MAX_BINS 64
+#define CCFD_GBDT_MAX_SPLITS 8
+// Level histograms: G[leaf(i)][f][rows[i][f]] += grad[i] (H likewise with hess) for every row
+// and feature.  G / H are overwritten (the launch zeroes them first).  0 <= level <= 7,
+// 2 <= n_bins <= 64, n >= 1; a bin byte >= n_bins is a caller error and that (row, feature)
+// is skipped.  Sums are f32 in no fixed order: the last bits may differ from run to run.
+typedef struct ccfd_gbdt_hist_args {
+  const uint8_t* rows;   // device [n][32], 16-byte aligned
+  const float* grad;     // device [n]
+  const float* hess;     // device [n]
+  float* G;              // device out [2^level][30][n_bins]
+  float* H;              // device out [2^level][30][n_bins]
+  int64_t n;
+  int32_t n_bins;
+  int32_t level;         // d: splits chosen so far (only the first d entries below are read)
+  int32_t split_feat[CCFD_GBDT_MAX_SPLITS];
+  int32_t split_bin[CCFD_GBDT_MAX_SPLITS];
+} ccfd_gbdt_hist_args;   // 120 bytes
+int ccfd_gbdt_hist_launch(const ccfd_gbdt_hist_args* a, void* stream);
+
+// Close a tree: raw[i] += leaf_val[leaf(i)], then (grad / hess non-NULL, both or neither)
+// p = sigmoid(raw[i]), grad[i] = p - y[i], hess[i] = max(p (1 - p), 1e-6).  depth 1..8, n >= 1.
+typedef struct ccfd_gbdt_update_args {
+  const uint8_t* rows;    // device [n][32], 16-byte aligned
+  const float* leaf_val;  // device [2^depth]
+  float* raw;             // device [n], updated in place
+  const float* y;         // device [n] labels (read only when grad / hess are given)
+  float* grad;            // device out [n], may be NULL
+  float* hess;            // device out [n], may be NULL
+  int64_t n;
+  int32_t depth;
+  int32_t pad;
+  int32_t split_feat[CCFD_GBDT_MAX_SPLITS];
+  int32_t split_bin[CCFD_GBDT_MAX_SPLITS];
+} ccfd_gbdt_update_args;  // 128 bytes
+int ccfd_gbdt_update_launch(const ccfd_gbdt_update_args* a, void* stream);
+
+// ---------------------------------------------------------------------------
 // Persistent streaming kernel (exec_mode = 1): ONE long-running launch per engine; the
 // host publishes micro-batch descriptors into a ring in coherent pinned memory and bumps
 // `posted`; resident workgroups claim 64..256-row work items with one device atomic, wait for

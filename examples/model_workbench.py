@@ -29,6 +29,8 @@ def main(argv=None) -> dict:
     ap.add_argument("--csv", default="")
     ap.add_argument("--rows", type=int, default=200_000)
     ap.add_argument("--trees", type=int, default=100)
+    ap.add_argument("--hist", default="torch", choices=["torch", "hip", "auto"],
+                    help="GBDT histogram backend (train_oblivious_gbdt hist=)")
     ap.add_argument("--epochs", type=int, default=3)
     ap.add_argument("--batch", type=int, default=8192)
     ap.add_argument("--device", default="auto", help="auto | cpu | cuda:N")
@@ -59,7 +61,8 @@ def main(argv=None) -> dict:
     # %% train the three model families
     cfg = TrainConfig(epochs=a.epochs, batch=a.batch, device=device)
     models = {"lr": train_logistic(Xtr, ytr, cfg)[0], "mlp": train_mlp(Xtr, ytr, cfg)[0],
-              "gbdt": train_oblivious_gbdt(Xtr, ytr, n_trees=a.trees, depth=6, device=device)[0]}
+              "gbdt": train_oblivious_gbdt(Xtr, ytr, n_trees=a.trees, depth=6, device=device,
+                                           hist=a.hist)[0]}
     report = {"rows": int(len(X)), "device": device, "models": {}}
     for name, m in models.items():
         r = evaluate(m, Xte, yte)
