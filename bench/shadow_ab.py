@@ -1,9 +1,15 @@
-"""What a shadow (challenger) MLP costs the streaming engine: shadow off / on legs, alternated
+"""What a shadow (challenger) model costs the streaming engine: shadow off / on legs, alternated
 in one process on one engine per exec mode, with bench.py config 2's engine settings (MLP on W64
 rows, micro-batch 4096, depth 12, zero-copy in both directions, flagged ring drained by a
-collector thread).
+collector thread) -- or, with ``--model gbdt``, config 4's (oblivious GBDT 100 x 6 on G20 / G32
+rows, micro-batch 65536, depth 4 on G20 / 3 on G32).
 
     python bench/shadow_ab.py --out profiles/shadow [--seconds 4] [--rounds 2]
+    python bench/shadow_ab.py --model gbdt [--wire g20|g32] --out profiles/shadow_gbdt
+
+The GBDT challenger is "a retrained ensemble inside the live bin table": the champion's splits
+with leaves of its own, packed against the champion's table -- what a hot swap without
+re-encoding the logs allows, and on the GPU the same work as any ensemble of that shape.
 
 Writes one JSON line per leg (tx/s, p50 / p99 micro-batch latency) and a summary line per exec
 mode (on/off ratio next to the spread between the off legs) to <out>/shadow_ab.jsonl.
@@ -47,16 +53,26 @@ def leg(eng, seconds: float, batches_per_step: int):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--out", default="profiles/shadow")
+    ap.add_argument("--model", default="mlp", choices=["mlp", "gbdt"])
+    ap.add_argument("--wire", default="g20", choices=["g20", "g32"], help="--model gbdt: binned row format")
+    ap.add_argument("--trees", type=int, default=100, help="--model gbdt: trees of both ensembles")
+    ap.add_argument("--tree-depth", type=int, default=6, help="--model gbdt: depth of both ensembles")
+    ap.add_argument("--out", default=None, help="default: profiles/shadow (mlp), profiles/shadow_gbdt (gbdt)")
     ap.add_argument("--seconds", type=float, default=4.0, help="length of one leg")
     ap.add_argument("--rounds", type=int, default=2, help="off/on pairs per exec mode")
-    ap.add_argument("--batch", type=int, default=4096)
-    ap.add_argument("--depth", type=int, default=12)
+    ap.add_argument("--batch", type=int, default=None, help="default: 4096 (mlp), 65536 (gbdt)")
+    ap.add_argument("--depth", type=int, default=None, help="default: 12 (mlp), 4 (gbdt on G20), 3 (gbdt on G32)")
     ap.add_argument("--streams", type=int, default=4)
     ap.add_argument("--log-rows", type=int, default=1 << 21)
     ap.add_argument("--batches-per-step", type=int, default=256)
-    ap.add_argument("--modes", default="persistent:8,launch:8,launch:1", help="exec_mode:coalesce, comma-separated")
+    ap.add_argument("--modes", default=None, help="exec_mode:coalesce, comma-separated (default: "
+                    "persistent:8,launch:8,launch:1 for mlp; persistent:1,launch:1 for gbdt, which is never coalesced)")
     a = ap.parse_args(argv)
+    gbdt = a.model == "gbdt"
+    a.out = a.out or ("profiles/shadow_gbdt" if gbdt else "profiles/shadow")
+    a.batch = a.batch or (65536 if gbdt else 4096)
+    a.depth = a.depth or ((4 if a.wire == "g20" else 3) if gbdt else 12)
+    a.modes = a.modes or ("persistent:1,launch:1" if gbdt else "persistent:8,launch:8,launch:1")
 
     import torch
 
@@ -66,12 +82,22 @@ def main(argv=None):
     from ccfd_demo_summit_amd.ops.kernels import DeviceModel
     dev = torch.device("cuda", 0)
     Xr, _ = generate(100_000, seed=17)
-    champion = DeviceModel(build_model("mlp", seed=0, X_ref=Xr, calibrate_rate=FRAUD_RATE), dev, wire=True)
-    shadow = DeviceModel(build_model("mlp", seed=1, X_ref=Xr, calibrate_rate=FRAUD_RATE), dev, wire=True)
+    bins = None
+    if gbdt:
+        from ccfd_demo_summit_amd.models.gbdt import ObliviousGBDT
+        mA = build_model("gbdt", seed=0, X_ref=Xr, calibrate_rate=FRAUD_RATE, gbdt_trees=a.trees,
+                         gbdt_depth=a.tree_depth)
+        bins = mA.bin_spec(bits=5 if a.wire == "g20" else 8)
+        mB = ObliviousGBDT(mA.feat, mA.thr, build_model("gbdt", seed=1, gbdt_trees=a.trees, gbdt_depth=a.tree_depth).leaves, 0.0)
+        mB.calibrate_bias(Xr, FRAUD_RATE)
+        champion, shadow = DeviceModel(mA, dev, bins=bins), DeviceModel(mB, dev, bins=bins)
+    else:
+        champion = DeviceModel(build_model("mlp", seed=0, X_ref=Xr, calibrate_rate=FRAUD_RATE), dev, wire=True)
+        shadow = DeviceModel(build_model("mlp", seed=1, X_ref=Xr, calibrate_rate=FRAUD_RATE), dev, wire=True)
     parts = 2
     logs = []
     for p in range(parts):
-        log = PartitionLog(a.log_rows // parts, wire=True)
+        log = PartitionLog(max(a.log_rows // parts, 4 * a.batch), wire=not gbdt, bins=bins)
         Xp, _ = generate(log.n, seed=7919 + p)
         log.write_rows(0, Xp)
         log.ids.array[:] = np.arange(log.n, dtype=np.uint64) + np.uint64(p) * np.uint64(1 << 40)
@@ -101,7 +127,9 @@ def main(argv=None):
                     eng.set_shadow(shadow if which == "on" else None)
                     out = leg(eng, a.seconds, a.batches_per_step)
                     res[which].append(out)
-                    emit(dict(out, kind="leg", exec_mode=mode, shadow=which, round=r, batch=a.batch, depth=a.depth,
+                    emit(dict(out, kind="leg", model=a.model, rows_format=champion.row_format, exec_mode=mode,
+                              shadow=which, round=r, batch=a.batch, depth=a.depth,
+                              **({"trees": a.trees, "tree_depth": a.tree_depth} if gbdt else {}),
                               coalesce=0 if mode != "launch" else 1 if which == "on" else int(co)))
             c = (eng.counters[0] + eng.counters[1]).cpu().numpy()
             sc = StreamEngine.shadow_counters(c)
@@ -110,7 +138,8 @@ def main(argv=None):
             eng.close()
             off = [x["tx_per_s"] for x in res["off"]]
             on = [x["tx_per_s"] for x in res["on"]]
-            emit({"kind": "summary", "exec_mode": mode, "coalesce": int(co) if mode == "launch" else 0,
+            emit({"kind": "summary", "model": a.model, "rows_format": champion.row_format, "exec_mode": mode, "coalesce": int(co) if mode == "launch" else 0,
+                  **({"trees": a.trees, "tree_depth": a.tree_depth} if gbdt else {}),
                   "off_tx_per_s": off, "on_tx_per_s": on,
                   "on_off_ratio": float(np.mean(on) / np.mean(off)),
                   "off_spread": float((max(off) - min(off)) / np.mean(off)),

@@ -98,7 +98,7 @@ class EngineConfig:
     ingest_threads: int = 0          # native Kafka consumer threads per rank (partitions split; 0 = auto:
                                      # one per partition for GBDT's binned rows, else 1)
     model_watch: str = ""            # hot-swap when this safetensors file changes (rank 0)
-    shadow_model: str = ""           # challenger MLP (safetensors) scored beside the live model, counters only
+    shadow_model: str = ""           # challenger (safetensors MLP, or GBDT on binned rows) scored beside the live model, counters only
     output_mode: str = "zerocopy"    # zerocopy (kernel writes pinned host) | dma
     exec_mode: str = "auto"          # persistent | launch | auto (persistent for zero-copy in/out:
                                      # the mode bench.py measures; launch_/engine_service.py)

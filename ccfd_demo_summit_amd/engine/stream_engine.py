@@ -326,11 +326,12 @@ class StreamEngine:
         one launch (MLP, zero-copy in/out); completion stays per micro-batch.
         rules: a compiled routing rule set (ops.kernels.DeviceRules) evaluated per row in the
         kernels' epilogue instead of ``proba >= threshold`` (kept alive by the engine).
-        shadow: a challenger MLP scored beside ``dm`` on the same rows in the same kernel pass
+        shadow: a challenger model scored beside ``dm`` on the same rows in the same kernel pass
         (``set_shadow``); the engine publishes its results as counters only
-        (``shadow_counters``).  MLP on W64 rows, threshold route, claimed persistent items of
-        128 / 256 / 512 rows; while one is set a launch-mode engine submits one launch per
-        micro-batch (``coalesce`` is not applied)."""
+        (``shadow_counters``).  An MLP pair on W64 rows (claimed persistent items of 128 / 256 /
+        512 rows) or an oblivious-GBDT pair of one shape on G32 / G20 rows of one bin table
+        (any item size); threshold route, claimed items; while one is set a launch-mode engine
+        submits one launch per micro-batch (``coalesce`` is not applied)."""
         if shadow is not None:           # refused before the native engine exists
             check_shadow_pair(dm, shadow, rules=rules, persist_items=2 if persist_items == "pipelined" else 0)
         self.shadow: Optional[DeviceModel] = None
@@ -508,8 +509,9 @@ class StreamEngine:
         self.model_version = getattr(self, "model_version", 0) + 1
 
     def set_shadow(self, dm: Optional[DeviceModel]) -> None:
-        """Score ``dm`` (a challenger MLP, W64 blob) beside the champion from the next
-        micro-batch on, or stop doing so (``None``).  Like ``swap_model``: in-flight
+        """Score ``dm`` (a challenger the champion could be swapped for: a W64 MLP blob, or a
+        GBDT of the champion's shape packed against the live bin table) beside the champion from
+        the next micro-batch on, or stop doing so (``None``).  Like ``swap_model``: in-flight
         micro-batches finish first.  The shadow's results are the ``CNT_SHADOW_*`` slots of the
         epoch counters (``shadow_counters``); the engine keeps ``dm`` alive."""
         if dm is not None:

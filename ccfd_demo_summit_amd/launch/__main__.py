@@ -418,10 +418,13 @@ def cmd_engine(a, cfg):
     shadow = None
     if settings.shadow_model:
         # the challenger: loaded on rank 0, broadcast like the live model so every rank scores
-        # the same blob; set before streaming starts (refused unless both are MLPs on W64 rows)
+        # the same blob; set before streaming starts (refused unless both are MLPs on W64 rows
+        # or GBDTs of one shape on binned rows).  A GBDT challenger is packed against the live
+        # bin table: the logs are encoded with it, and a threshold that is not one of its edges
+        # is the BinSpec error
         from ..models import load_model
         shadow = broadcast_model(ctx, load_model(settings.shadow_model) if ctx.rank == 0 else None,
-                                 cfg.engine.model, dm.row_format)
+                                 cfg.engine.model, dm.row_format, bins=getattr(dm, "bins", None))
         print(f"[engine] shadow model {settings.shadow_model}: scored beside the live model, counters only",
               flush=True)
     svc = EngineService(ctx, dm, broker, router, settings, shadow=shadow).start()
@@ -713,7 +716,10 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--port", type=int, default=None)
     ap.add_argument("--watch-model", default=None, help="engine: hot-swap weights when this file changes")
     ap.add_argument("--shadow-model", default=None,
-                    help="engine: safetensors MLP scored beside the live model on the same rows "
+                    help="engine: safetensors challenger scored beside the live model on the same rows -- an MLP "
+                         "beside an MLP on W64 rows, or an oblivious GBDT of the live ensemble's shape beside a "
+                         "GBDT on G32 / G20 rows (packed against the live bin table; train it with "
+                         "`train --bin-spec-from`) "
                          "(shadow counters and ccfd_gpu_shadow_* series only; promote it with --watch-model)")
     ap.add_argument("--model-metrics-port", type=int, default=None,
                     help="engine: port (+ local rank) of the model's /prometheus (proba_1 / Amount / V17 / V10, "

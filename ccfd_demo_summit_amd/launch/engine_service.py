@@ -115,7 +115,8 @@ def resolve_exec_mode(exec_mode: str, model_kind: str, row_format: str, input_mo
 class EngineService:
     def __init__(self, ctx, dm, broker, router, cfg: EngineServiceConfig, reducer=None, partitions=None,
                  shadow=None):
-        """``shadow``: a challenger DeviceModel (MLP, W64 rows) scored beside ``dm`` from the
+        """``shadow``: a challenger DeviceModel (an MLP on W64 rows, or a GBDT of ``dm``'s shape
+        packed against ``dm``'s G32 / G20 bin table) scored beside ``dm`` from the
         first micro-batch on; its results are the shadow counter slots of the X2 all-reduce and
         the ``ccfd_gpu_shadow_*`` series (engine.StreamEngine.set_shadow)."""
         from ..engine import StreamEngine

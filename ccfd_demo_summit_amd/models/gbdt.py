@@ -221,6 +221,27 @@ class ObliviousGBDT:
         spec = BinSpec.from_thresholds(self.feat, self.thr)
         return spec if bits == 8 else spec.with_bits(bits)
 
+    def padded(self, n_trees: Optional[int] = None, depth: Optional[int] = None) -> "ObliviousGBDT":
+        """An exactly equivalent ensemble of a larger shape (e.g. a challenger brought to the
+        champion's shape for shadow scoring or a hot swap).  Added levels test ``x[0] > NaN``
+        -- never true, packed as bin index 255 -- so a row's leaf index keeps its value and the
+        original leaves sit in the low ``2^d`` entries; added trees have all-NaN splits and zero
+        leaves.  ``raw_score`` is bit-identical.  A request to shrink raises ``ValueError``."""
+        T, D = self.feat.shape
+        T2 = T if n_trees is None else int(n_trees)
+        D2 = D if depth is None else int(depth)
+        if T2 < T or D2 < D:
+            raise ValueError(f"padded() cannot shrink a {T} x depth {D} ensemble to {T2} x depth {D2}")
+        if D2 > MAX_DEPTH:
+            raise ValueError(f"depth must be in [1,{MAX_DEPTH}]")
+        feat = np.zeros((T2, D2), np.int32)
+        thr = np.full((T2, D2), np.nan, np.float32)
+        leaves = np.zeros((T2, 1 << D2), np.float32)
+        feat[:T, :D] = self.feat
+        thr[:T, :D] = self.thr
+        leaves[:T, :1 << D] = self.leaves
+        return ObliviousGBDT(feat, thr, leaves, self.base)
+
     def pack(self, wire: bool = False, bins: Optional[BinSpec] = None) -> bytes:
         """GBT1 blob for f32 rows, or (``bins``) the GBB1 blob for G32 rows of that spec."""
         if wire:

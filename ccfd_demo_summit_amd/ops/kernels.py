@@ -100,21 +100,39 @@ def new_counters(device="cuda") -> torch.Tensor:
 
 def check_shadow_pair(dm: DeviceModel, shadow: DeviceModel, rules=None, persist_items: int = 0) -> None:
     """Refuse (``ValueError`` naming the combination) every champion / shadow pair the shadow
-    kernels do not cover: both must be MLPs packed for W64 rows (``DeviceModel(..., wire=True)``),
-    routed by ``proba >= threshold`` (no ``rules``), and a persistent engine must use claimed
-    items (``persist_items`` 0 / 1, not the pipelined 2).  Pure host check: no launch, no GPU."""
+    kernels do not cover.  Covered: two MLPs packed for W64 rows (``DeviceModel(..., wire=True)``),
+    or two oblivious GBDTs of the same ``(trees, depth)`` packed against the same G32 / G20 bin
+    table (``DeviceModel(model, bins=spec)``; ``ObliviousGBDT.padded`` brings a smaller
+    challenger to the champion's shape).  Either pair is routed by ``proba >= threshold`` (no
+    ``rules``), and a persistent engine must use claimed items (``persist_items`` 0 / 1, not the
+    pipelined 2).  Pure host check: no launch, no GPU."""
     from ..models.mlp import WIRE_BLOB_BYTES
     if dm.kind != shadow.kind:
         raise ValueError(f"shadow model: kind mismatch, champion is {dm.kind!r} and shadow is {shadow.kind!r} "
                          "(a shadow is a candidate for swap_model: same kind and shape)")
-    if dm.kind != "mlp":
-        raise ValueError(f"shadow model: {dm.kind!r} models have no shadow kernel (MLP on W64 rows only)")
-    for role, m in (("champion", dm), ("shadow", shadow)):
-        if m.row_format != "w64":
-            raise ValueError(f"shadow model: the {role} MLP is packed for {m.row_format} rows; "
-                             "both blobs must be packed for W64 rows (DeviceModel(..., wire=True))")
-        if m.blob.numel() * m.blob.element_size() != WIRE_BLOB_BYTES:
-            raise ValueError(f"shadow model: the {role} blob is not a {WIRE_BLOB_BYTES}-byte W64 MLP blob")
+    if dm.kind == "gbdt" and (dm.row_format in BIN_FORMATS or shadow.row_format in BIN_FORMATS):
+        from ..engine.stream_engine import same_bins
+        if dm.row_format != shadow.row_format:
+            raise ValueError(f"shadow model: the champion GBDT is packed for {dm.row_format} rows and the shadow "
+                             f"for {shadow.row_format} rows; both must be packed for the same binned format")
+        if not same_bins(dm.bins, shadow.bins):
+            raise ValueError(f"shadow model: the champion's and the shadow's {dm.row_format} bin tables differ "
+                             f"(stamps {dm.bins.stamp} and {shadow.bins.stamp}); pack the shadow against the "
+                             "champion's table (DeviceModel(model, bins=champion.bins))")
+        if (dm.trees, dm.depth) != (shadow.trees, shadow.depth):
+            raise ValueError(f"shadow model: shape mismatch, the champion is {dm.trees} trees x depth {dm.depth} and "
+                             f"the shadow is {shadow.trees} trees x depth {shadow.depth} "
+                             "(ObliviousGBDT.padded brings a smaller ensemble to the champion's shape)")
+    elif dm.kind != "mlp":
+        raise ValueError(f"shadow model: {dm.kind!r} models have no shadow kernel (MLP on W64 rows, or "
+                         "oblivious GBDT on G32 / G20 rows: DeviceModel(model, bins=...))")
+    else:
+        for role, m in (("champion", dm), ("shadow", shadow)):
+            if m.row_format != "w64":
+                raise ValueError(f"shadow model: the {role} MLP is packed for {m.row_format} rows; "
+                                 "both blobs must be packed for W64 rows (DeviceModel(..., wire=True))")
+            if m.blob.numel() * m.blob.element_size() != WIRE_BLOB_BYTES:
+                raise ValueError(f"shadow model: the {role} blob is not a {WIRE_BLOB_BYTES}-byte W64 MLP blob")
     if rules is not None:
         raise ValueError("shadow model: routing rules present; a shadow routes by proba >= threshold only")
     if int(persist_items) == 2:
@@ -131,9 +149,10 @@ def score(dm: DeviceModel, x: torch.Tensor, threshold: float = 0.5,
     ([n,64] uint8 or [n,16] float32 view), for a ``bins`` model G32 / G20 rows ([n,32] / [n,20] u8) --
     returns (proba_1 [n] f32, route [n] u8).
     ``flags``: extra ``CCFD_ARG_*`` bits (ablation switches for profiling).
-    ``shadow``: a challenger MLP (W64 blob, like ``dm``) scored on the same rows in the same
-    pass; returns (proba_1, route, shadow proba_1 [n] f32) and adds the ``CNT_SHADOW_*``
-    counters (``check_shadow_pair`` lists what is refused)."""
+    ``shadow``: a challenger scored on the same rows in the same pass -- an MLP (W64 blob, like
+    ``dm``), or an oblivious GBDT of ``dm``'s shape packed against ``dm``'s G32 / G20 bin table;
+    returns (proba_1, route, shadow proba_1 [n] f32) and adds the ``CNT_SHADOW_*`` counters
+    (``check_shadow_pair`` lists what is refused)."""
     if shadow is not None:
         check_shadow_pair(dm, shadow, rules=rules)
     elif shadow_proba is not None:

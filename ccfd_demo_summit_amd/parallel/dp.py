@@ -137,7 +137,7 @@ def resolve_row_format(kind: str, wire: str = "auto") -> str:
     return wire
 
 
-def broadcast_model(ctx: DistContext, model, kind: str, row_format: str, group=None):
+def broadcast_model(ctx: DistContext, model, kind: str, row_format: str, group=None, bins=None):
     """X1 for a whole device model: rank 0 packs ``model`` for ``row_format`` (f32 / w64 /
     g32) and broadcasts the blob -- plus, for G32, the bin table every rank encodes its
     partition logs with, and the tree shape; every rank returns an equal DeviceModel.
@@ -147,7 +147,12 @@ def broadcast_model(ctx: DistContext, model, kind: str, row_format: str, group=N
     (u8 bins).  An ensemble with more widens to the next format (G20 -> G32 -> f32 rows) on
     every rank: rank 0 decides and the decision travels in the header broadcast ahead of
     the blob, so all ranks agree.  Callers take the row format from the returned model
-    (``DeviceModel.row_format``)."""
+    (``DeviceModel.row_format``).
+
+    ``bins`` (a ``BinSpec`` every rank already holds, e.g. the live model's ``dm.bins``): pack
+    against that table and use its format instead of the ensemble's own table -- a challenger
+    or a hot-swap candidate for logs that are already encoded.  ``ValueError`` on rank 0 (the
+    ``BinSpec`` error) if a threshold of the ensemble is not an edge of the table."""
     from ..models.gbdt import BinSpec
     from ..ops.kernels import DeviceModel
     codes = {"f32": 0, "w64": 1, "g32": 2, "g20": 3}
@@ -155,13 +160,15 @@ def broadcast_model(ctx: DistContext, model, kind: str, row_format: str, group=N
     header = torch.zeros(3, dtype=torch.int64, device=ctx.device)      # trees, depth, row format
     if ctx.rank == 0:
         fmt = row_format
-        if fmt == "g20":
+        if bins is not None:
+            spec, fmt = bins, bins.row_format
+        elif fmt == "g20":
             try:
                 spec = model.bin_spec(bits=5)
             except ValueError as e:                 # > 31 thresholds on a feature
                 warnings.warn(f"G20 rows impossible for this ensemble ({e}); trying G32 rows")
                 fmt = "g32"
-        if fmt == "g32":
+        if fmt == "g32" and bins is None:
             try:
                 spec = model.bin_spec()
             except ValueError as e:                 # > 255 thresholds on a feature
@@ -179,8 +186,7 @@ def broadcast_model(ctx: DistContext, model, kind: str, row_format: str, group=N
         dist.broadcast(header, 0, group=group)
     fmt = {v: k for k, v in codes.items()}[int(header[2])]
     blob = broadcast_blob(ctx, blob, group=group)
-    bins = None
-    if fmt in ("g32", "g20"):
+    if fmt in ("g32", "g20") and bins is None:
         bins = BinSpec.from_bytes(broadcast_blob(ctx, spec_t, group=group).cpu().numpy().tobytes(),
                                   bits=8 if fmt == "g32" else 5)
     return DeviceModel.from_blob(kind, blob, int(header[0]), int(header[1]), wire=fmt == "w64", bins=bins)

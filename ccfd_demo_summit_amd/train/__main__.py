@@ -65,6 +65,10 @@ def main(argv=None) -> int:
     ap.add_argument("--hist", default="torch", choices=["torch", "hip", "auto"],
                     help="GBDT: histogram backend -- torch scatter_add (default), the HIP histogram kernel over "
                          "G32 rows (CUDA device, <= 64 bins), or auto (hip when it can)")
+    ap.add_argument("--bin-spec-from", default=None, metavar="MODEL.safetensors",
+                    help="GBDT: take the split candidates from this GBDT's bin table (its bin_spec()), so the "
+                         "trained ensemble packs against the table the live G32 / G20 logs were encoded with "
+                         "(a challenger for `launch engine --shadow-model`); replaces --max-borders")
     ap.add_argument("--metrics-port", type=int, default=0,
                     help="serve the trainer's /metrics (the SparkMetrics dashboard series) on this port "
                          "(+ rank) while training; 0 = off")
@@ -122,9 +126,18 @@ def main(argv=None) -> int:
     dev = a.device
     if world > 1 and dev == "auto" and torch.cuda.is_available():
         dev = f"cuda:{torch.cuda.current_device()}"
+    if a.bin_spec_from and a.model != "gbdt":
+        raise SystemExit("--bin-spec-from is for --model gbdt")
     if a.model == "gbdt":
+        spec = None
+        if a.bin_spec_from:
+            from ..models import load_model
+            live = load_model(a.bin_spec_from)
+            if live.kind != "gbdt":
+                raise SystemExit(f"--bin-spec-from {a.bin_spec_from}: a {live.kind!r} model has no bin table")
+            spec = live.bin_spec()
         model, info = train_oblivious_gbdt(X[tr], y[tr], n_trees=a.trees, depth=a.depth, device=dev,
-                                           n_bins=a.max_borders + 1, hist=a.hist)
+                                           n_bins=a.max_borders + 1, hist=a.hist, bin_spec=spec)
     else:
         cfg = TrainConfig(epochs=a.epochs, batch=a.batch, device=dev, seed=a.seed, metrics=tm)
         model, info = (train_mlp if a.model == "mlp" else train_logistic)(X[tr], y[tr], cfg)

@@ -217,16 +217,22 @@ def _hip_hist_refusal(dev: torch.device, n_bins: int, depth: int, n_features: in
     return None
 
 
-def _encode_training_rows(X: np.ndarray, borders: np.ndarray) -> np.ndarray:
+def _encode_training_rows(X: np.ndarray, borders: np.ndarray, counts: Optional[np.ndarray] = None) -> np.ndarray:
     """X [n, 30] f32 -> G32 rows [n, 32] u8 against ``borders`` [30, B-1] as a bin table
     (native encoder, csrc/engine/ingest.cpp): byte j = #borders_j < x_j, the trainer's
-    ``searchsorted(..., "left")``, except that NaN goes to bin 0."""
+    ``searchsorted(..., "left")``, except that NaN goes to bin 0.  ``counts`` [30]: only the
+    first ``counts[j]`` borders of feature j are edges (a ragged table, ``bin_spec=``)."""
     import os
     from ..ops._lib import lib
     X = np.ascontiguousarray(X, np.float32)
     n, F = X.shape
-    flat = np.ascontiguousarray(borders, np.float32).reshape(-1)
-    offsets = (np.arange(F + 1, dtype=np.int32) * np.int32(borders.shape[1])).astype(np.int32)
+    if counts is None:
+        flat = np.ascontiguousarray(borders, np.float32).reshape(-1)
+        offsets = (np.arange(F + 1, dtype=np.int32) * np.int32(borders.shape[1])).astype(np.int32)
+    else:
+        flat = np.concatenate([borders[f, :counts[f]] for f in range(F)] + [np.zeros(1, np.float32)]).astype(np.float32)
+        offsets = np.zeros(F + 1, np.int32)
+        np.cumsum(counts, out=offsets[1:])
     rows = np.empty((n, 32), np.uint8)
     threads = max(1, min(16, os.cpu_count() or 1, (n + 65535) // 65536))
     if lib().ccfd_encode_bins_mt(X.ctypes.data, n, F, flat.ctypes.data, offsets.ctypes.data, 1, 0,
@@ -236,10 +242,12 @@ def _encode_training_rows(X: np.ndarray, borders: np.ndarray) -> np.ndarray:
 
 
 def _boost_hip(rows: torch.Tensor, yt: torch.Tensor, raw: torch.Tensor, borders: np.ndarray, feat: np.ndarray,
-               thr: np.ndarray, leaves: np.ndarray, l2: float, learning_rate: float, allreduce) -> None:
+               thr: np.ndarray, leaves: np.ndarray, l2: float, learning_rate: float, allreduce,
+               padded: Optional[torch.Tensor] = None) -> None:
     """The boosting loop of ``train_oblivious_gbdt(hist="hip")``: fills feat / thr / leaves and
     advances ``raw`` in place.  Per level one histogram launch over the G32 ``rows``, then the
-    all-reduce and the gain scan of the torch path; per tree one update launch."""
+    all-reduce and the gain scan of the torch path; per tree one update launch.  ``padded``
+    [F, B-1] bool: candidates that are padding of a ragged border matrix (never chosen)."""
     from ..ops.kernels import gbdt_apply_tree, gbdt_histogram
     n_trees, depth = feat.shape
     B = borders.shape[1] + 1
@@ -257,6 +265,8 @@ def _boost_hip(rows: torch.Tensor, yt: torch.Tensor, raw: torch.Tensor, borders:
             Ht = H.sum(-1, keepdim=True)
             Gr, Hr = Gt - Gl, Ht - Hl
             gain = (Gl ** 2 / (Hl + l2) + Gr ** 2 / (Hr + l2) - Gt ** 2 / (Ht + l2)).sum(0)   # [F, B-1]
+            if padded is not None:
+                gain = gain.masked_fill(padded, float("-inf"))
             best = int(torch.argmax(gain))
             f, b = divmod(best, B - 1)
             feat[t, d] = f
@@ -274,7 +284,7 @@ def _boost_hip(rows: torch.Tensor, yt: torch.Tensor, raw: torch.Tensor, borders:
 def train_oblivious_gbdt(X: np.ndarray, y: np.ndarray, n_trees: int = 100, depth: int = 6,
                          learning_rate: float = 0.1, n_bins: int = 32, l2: float = 1.0,
                          device: str = "auto", borders: Optional[np.ndarray] = None,
-                         hist: str = "torch") -> Tuple[ObliviousGBDT, Dict]:
+                         hist: str = "torch", bin_spec=None) -> Tuple[ObliviousGBDT, Dict]:
     """Level-wise oblivious boosting on logloss.  At each level one (feature, border) is
     chosen for ALL current leaves (maximum summed second-order gain).
 
@@ -285,7 +295,13 @@ def train_oblivious_gbdt(X: np.ndarray, y: np.ndarray, n_trees: int = 100, depth
     the leaf sums and the base-rate statistics are all-reduced (SUM), so every rank grows
     the same trees -- the ones a single process would grow on the union of the shards, up to
     float summation order.  ``borders`` [F, n_bins-1]: use these split candidates instead of
-    quantiles of X.
+    quantiles of X.  ``bin_spec`` (a ``models.gbdt.BinSpec``, e.g. the table the live partition
+    logs were encoded with): the split candidates of feature f are exactly ``bin_spec.edges[f]``,
+    so ``bin_spec.contains(model.bin_spec())`` holds and ``DeviceModel(model, bins=bin_spec)``
+    always packs -- a challenger for live G32 / G20 logs is trained without re-encoding them.
+    The table may be ragged (``B = max_f len(edges_f) + 1`` bins; the border matrix is padded
+    with ``+inf`` and a padded candidate is never chosen); ``ValueError`` if it is given together
+    with ``borders`` or if no feature has an edge.
 
     ``hist`` picks how the histograms are built; ``info["hist"]`` reports the path used.
 
@@ -317,6 +333,18 @@ def train_oblivious_gbdt(X: np.ndarray, y: np.ndarray, n_trees: int = 100, depth
         return t
 
     X = np.asarray(X, np.float32)
+    counts = None
+    if bin_spec is not None:
+        if borders is not None:
+            raise ValueError("bin_spec= and borders= both name the split candidates: give one of them")
+        counts = np.array([e.size for e in bin_spec.edges], np.int32)
+        if len(counts) != X.shape[1]:
+            raise ValueError(f"bin_spec has {len(counts)} features, X has {X.shape[1]}")
+        if counts.max(initial=0) == 0:
+            raise ValueError("bin_spec has no edge on any feature: there is no split candidate")
+        borders = np.full((len(counts), int(counts.max())), np.inf, np.float32)
+        for f, e in enumerate(bin_spec.edges):
+            borders[f, :e.size] = e
     use_hip = False
     if hist != "torch":
         why = _hip_hist_refusal(dev, n_bins if borders is None else np.shape(borders)[1] + 1, depth, X.shape[1])
@@ -337,12 +365,15 @@ def train_oblivious_gbdt(X: np.ndarray, y: np.ndarray, n_trees: int = 100, depth
         borders = bt0.cpu().numpy()
     # bin index of every value: number of borders strictly below it -> x > border[b] iff bin > b
     if use_hip:
-        rows = torch.from_numpy(_encode_training_rows(X, borders)).to(dev)      # [n, 32] u8
+        rows = torch.from_numpy(_encode_training_rows(X, borders, counts)).to(dev)      # [n, 32] u8
     else:
         bins = np.empty((n, F), np.int64)
-        for f in range(F):
-            bins[:, f] = np.searchsorted(borders[f], X[:, f], side="left")
+        for f in range(F):                                          # a ragged table: the real edges only
+            bins[:, f] = np.searchsorted(borders[f] if counts is None else borders[f, :counts[f]], X[:, f], side="left")
         bt = torch.from_numpy(bins).to(dev)
+    # padding of a ragged border matrix: gain -inf before the argmax
+    padded = None if counts is None else \
+        (torch.arange(n_bins - 1, device=dev)[None, :] >= torch.from_numpy(counts).to(dev)[:, None])
     yt = torch.from_numpy(y.astype(np.float32)).to(dev)
     stats = allreduce(torch.tensor([float(y.sum()), float(n)], dtype=torch.float64, device=dev))
     p0 = float(np.clip(float(stats[0]) / max(float(stats[1]), 1.0), 1e-6, 1 - 1e-6))
@@ -356,7 +387,7 @@ def train_oblivious_gbdt(X: np.ndarray, y: np.ndarray, n_trees: int = 100, depth
     import time as _time
     t_boost = _time.perf_counter()
     if use_hip:
-        _boost_hip(rows, yt, raw, borders, feat, thr, leaves, l2, learning_rate, allreduce)
+        _boost_hip(rows, yt, raw, borders, feat, thr, leaves, l2, learning_rate, allreduce, padded)
     for t in range(0 if use_hip else n_trees):                         # hist="torch"
         prob = torch.sigmoid(raw)
         grad = prob - yt
@@ -375,6 +406,8 @@ def train_oblivious_gbdt(X: np.ndarray, y: np.ndarray, n_trees: int = 100, depth
             Ht = H.sum(-1, keepdim=True)
             Gr, Hr = Gt - Gl, Ht - Hl
             gain = (Gl ** 2 / (Hl + l2) + Gr ** 2 / (Hr + l2) - Gt ** 2 / (Ht + l2)).sum(0)   # [F, B-1]
+            if padded is not None:
+                gain = gain.masked_fill(padded, float("-inf"))
             best = int(torch.argmax(gain))
             f, b = divmod(best, B - 1)
             feat[t, d] = f

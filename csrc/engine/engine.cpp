@@ -360,7 +360,7 @@ class Engine {
   int persist_C = 0;
   int persist_tpw = 1;
   bool persist_pipe = false;
-  const void* shadow_blob = nullptr;       // challenger MLP scored beside cfg.blob (set_shadow)
+  const void* shadow_blob = nullptr;       // challenger (MLP / GBDT) scored beside cfg.blob (set_shadow)
   int64_t completed_upto = 0;              // batches completed in order (seq count)
   std::vector<int64_t> flip_seq;           // seq at each epoch flip
 
@@ -1128,13 +1128,18 @@ class Engine {
   int set_shadow(const void* blob) {
     if (blob != nullptr) {
       static const char* const kKind[] = {"lr", "mlp", "gbdt", "forest"};
-      if (cfg.model != CCFD_MODEL_MLP) {
+      const bool gbdt = cfg.model == CCFD_MODEL_GBDT;
+      if (cfg.model != CCFD_MODEL_MLP && !gbdt) {
         set_error(std::string("shadow model refused: the engine's champion is ") +
                   (cfg.model >= 0 && cfg.model < 4 ? kKind[cfg.model] : "unknown") +
-                  "; only an MLP champion on W64 rows can carry a shadow");
+                  "; only an MLP champion on W64 rows or a GBDT champion on G32 / G20 rows can carry a shadow");
         return -1;
       }
-      if (cfg.wire != 1) {
+      if (gbdt && cfg.wire < 2) {
+        set_error("shadow model refused: the engine scores a GBDT on f32 rows; shadow scoring needs G32 / G20 rows");
+        return -1;
+      }
+      if (!gbdt && cfg.wire != 1) {
         set_error("shadow model refused: the engine scores an MLP on f32 rows; shadow scoring needs W64 rows");
         return -1;
       }
@@ -1147,7 +1152,8 @@ class Engine {
                   "have no shadow kernel; use claimed items");
         return -1;
       }
-      if (persistent && persist_tpw != 2 && persist_tpw != 4 && persist_tpw != 8) {
+      // a GBDT champion's items (256 / 512 / 1024 rows) all have a shadow kernel
+      if (!gbdt && persistent && persist_tpw != 2 && persist_tpw != 4 && persist_tpw != 8) {
         set_error("shadow model refused: persistent items of " + std::to_string(64 * persist_tpw) +
                   " rows; the shadow kernel takes items of 128, 256 or 512 rows");
         return -1;

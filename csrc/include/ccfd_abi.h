@@ -24,8 +24,9 @@ enum ccfd_counter_slot {
   CCFD_CNT_WIRE_STALE = 4,    // G32 / G20 rows whose bin stamp != the model's (proba NaN, standard route)
   CCFD_CNT_HIST_STD = 8,      // 14 amount buckets, standard route
   CCFD_CNT_HIST_FRAUD = 24,   // 14 amount buckets, fraud route
-  // Shadow (challenger) model scored beside the champion (score_shadow.hip); written only by
-  // the shadow kernels, so they stay zero while no shadow is set.
+  // Shadow (challenger) model scored beside the champion (score_shadow.hip,
+  // score_gbdt_shadow.hip); written only by the shadow kernels, so they stay zero while no
+  // shadow is set.  Stale G32 / G20 rows (slot 4) are counted in none of them.
   CCFD_CNT_SHADOW_ROWS = 40,        // valid rows the challenger scored
   CCFD_CNT_SHADOW_FRAUD = 41,       // rows the challenger routes as fraud
   CCFD_CNT_SHADOW_BOTH = 42,        // rows both models route as fraud
@@ -148,14 +149,19 @@ int ccfd_score_launch(const ccfd_score_args* a, void* stream);
 // library has launched with before (a recycled allocation).
 void ccfd_forest_blob_changed(const void* blob);
 
-// Shadow scoring: a challenger MLP scored beside the champion in the same pass over the rows
-// (score_shadow.hip).  Both blobs are MLPs packed for W64 rows and route by
-// `proba >= threshold`; base.rules must be NULL.  The champion's outputs, counters, flag list
-// and completion record are those of ccfd_score_launch; the challenger adds the
-// CCFD_CNT_SHADOW_* counters and, when shadow_proba is non-NULL, its proba_1 per row.
+// Shadow scoring: a challenger model scored beside the champion in the same pass over the rows.
+// Both blobs are MLPs packed for W64 rows (score_shadow.hip), or oblivious GBDTs packed for
+// the same G32 / G20 bin table (score_gbdt_shadow.hip; base.flags carries CCFD_ARG_WIRE_G32,
+// with CCFD_ARG_WIRE_G20 for G20 rows), and route by `proba >= threshold`; base.rules must be
+// NULL.  The champion's outputs, counters, flag list and completion record are those of
+// ccfd_score_launch; the challenger adds the CCFD_CNT_SHADOW_* counters and, when shadow_proba
+// is non-NULL, its proba_1 per row (NaN for a stale G32 / G20 row, like the champion's).
+// A GBDT shadow blob must have the champion's shape (base.gbdt_trees x base.gbdt_depth) and
+// bin stamp: the native side trusts that, as ccfd_engine_set_blob does -- the callers check
+// it (ops/kernels.py check_shadow_pair).  Refused: GBDT on f32 rows, LR, forest, rules.
 typedef struct ccfd_shadow_args {
   ccfd_score_args base;
-  const void* shadow_blob;   // device memory, MLP W64 blob
+  const void* shadow_blob;   // device memory: MLP W64 blob, or GBB1 blob of the champion's shape
   float* shadow_proba;       // out [n] (device or host-mapped), may be NULL
 } ccfd_shadow_args;
 int ccfd_score_launch_shadow(const ccfd_shadow_args* a, void* stream);
@@ -262,11 +268,14 @@ typedef struct ccfd_persist_args {
 
 int ccfd_persist_launch(const ccfd_persist_args* a, int grid, void* stream);
 
-// Persistent kernel with a shadow MLP: claimed W64 items of 2, 4 or 8 tiles per wave, MLP,
-// threshold route (no rules, no CCFD_ARG_PIPE_ITEMS); same host protocol as ccfd_persist_launch.
+// Persistent kernel with a shadow model: an MLP pair on claimed W64 items of 2, 4 or 8 tiles
+// per wave, or an oblivious-GBDT pair on claimed G32 / G20 items of 1, 2 or 4 chunks per wave
+// (256 / 512 / 1024 rows; the shadow blob has the champion's shape and bin stamp, trusted as
+// above); threshold route (no rules, no CCFD_ARG_PIPE_ITEMS); same host protocol as
+// ccfd_persist_launch.
 typedef struct ccfd_persist_shadow_args {
   ccfd_persist_args base;
-  const void* shadow_blob;   // device memory, MLP W64 blob
+  const void* shadow_blob;   // device memory: MLP W64 blob, or GBB1 blob of the champion's shape
 } ccfd_persist_shadow_args;
 int ccfd_persist_launch_shadow(const ccfd_persist_shadow_args* a, int grid, void* stream);
 
@@ -401,8 +410,11 @@ int ccfd_engine_set_blob(void* eng, const void* blob);
 // Shadow model (NULL = none): like set_blob, in-flight micro-batches drain and a resident
 // persistent kernel halts first; later submissions score the shadow beside the champion and
 // add the CCFD_CNT_SHADOW_* counters (no per-row shadow output).  Refused unless the engine
-// scores an MLP on W64 rows by threshold with claimed persistent items of 128 / 256 / 512 rows;
-// a launch-mode engine submits one launch per micro-batch (no coalescing) while one is set.
+// scores by threshold (no rule program) with claimed persistent items, and its champion is an
+// MLP on W64 rows (items of 128 / 256 / 512 rows) or an oblivious GBDT on G32 / G20 rows (any
+// item size; `blob` must have the champion's shape and bin table, which is trusted here as in
+// set_blob).  A launch-mode engine submits one launch per micro-batch (no coalescing) while
+// one is set.
 int ccfd_engine_set_shadow(void* eng, const void* blob);
 // Drain up to `max` flagged records (fraud route) into `out`; returns count.
 int64_t ccfd_engine_drain_flagged(void* eng, ccfd_flagged* out, int64_t max);

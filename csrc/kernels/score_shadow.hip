@@ -20,16 +20,21 @@
 // The challenger adds five counters (CCFD_CNT_SHADOW_*), accumulated per wave, then per
 // workgroup in LDS, then one set of atomics per workgroup (launch) or item (persistent); the
 // launch kernel also stores its proba_1 per row when asked to.  MLP on W64 rows, threshold
-// route only: everything else is refused on the host.
+// route only; the two entry points at the end of this file also hand an oblivious-GBDT pair on
+// G32 / G20 rows to its own kernels (score_gbdt_shadow.hip).  Everything else is refused on
+// the host.
 #include <string>
 #include <type_traits>
 
 #include "mlp_core.h"
 #include "persist_core.h"
+#include "shadow_core.h"
 
 namespace ccfd {
 
 void set_error(const std::string& e);   // dispatch.hip
+int launch_gbdt_shadow(const ccfd_shadow_args& sa, hipStream_t s);                         // score_gbdt_shadow.hip
+int launch_persist_gbdt_shadow(const ccfd_persist_shadow_args& sa, int grid, hipStream_t s);
 
 namespace {
 
@@ -39,50 +44,6 @@ constexpr int kShadowWaves = 4;          // waves per workgroup of the launch ke
 // workgroup per CU the grid-stride loop takes over (each workgroup stages 56 KB of weights).
 constexpr int kShadowTilesPerWave = 2;
 constexpr int kShadowGridCap = 256;
-
-// Per-workgroup accumulators of the challenger's counters.
-struct ShadowLds {
-  unsigned int rows, fraud, both, pad;
-  unsigned long long psum_e6, absdiff_e6;
-};
-
-struct ShadowAcc {                       // per wave, in registers
-  unsigned fraud = 0, both = 0;
-  unsigned long long psum = 0, absdiff = 0;
-};
-
-__device__ __forceinline__ void shadow_init(ShadowLds& s) {
-  if (threadIdx.x == 64) { s.rows = 0; s.fraud = 0; s.both = 0; s.pad = 0; s.psum_e6 = 0; s.absdiff_e6 = 0; }
-}
-
-// One row's challenger bookkeeping, in the lane that owns the row's outputs.
-__device__ __forceinline__ void shadow_row(ShadowAcc& w, float p, float q) {
-  w.psum += (unsigned)(q * 1e6f + 0.5f);                 // the rounding of CCFD_CNT_PROBA_E6
-  w.absdiff += (unsigned)(fabsf(p - q) * 1e6f + 0.5f);
-}
-
-// Wave -> workgroup: `rows` = valid rows this wave scored (wave-uniform).
-__device__ __forceinline__ void shadow_wave_commit(ShadowLds& s, ShadowAcc& w, unsigned rows, int lane) {
-  w.psum = wave_sum_u64(w.psum);
-  w.absdiff = wave_sum_u64(w.absdiff);
-  if (lane == 0 && rows) {
-    atomicAdd(&s.rows, rows);
-    atomicAdd(&s.fraud, w.fraud);
-    atomicAdd(&s.both, w.both);
-    atomicAdd(&s.psum_e6, w.psum);
-    atomicAdd(&s.absdiff_e6, w.absdiff);
-  }
-}
-
-// Workgroup -> global, one thread, after a barrier that follows every wave's commit.
-__device__ __forceinline__ void shadow_flush(const ShadowLds& s, unsigned long long* cnt) {
-  if (cnt == nullptr || s.rows == 0) return;
-  atomicAdd(&cnt[CCFD_CNT_SHADOW_ROWS], (unsigned long long)s.rows);
-  atomicAdd(&cnt[CCFD_CNT_SHADOW_FRAUD], (unsigned long long)s.fraud);
-  atomicAdd(&cnt[CCFD_CNT_SHADOW_BOTH], (unsigned long long)s.both);
-  atomicAdd(&cnt[CCFD_CNT_SHADOW_PROBA_E6], s.psum_e6);
-  atomicAdd(&cnt[CCFD_CNT_SHADOW_ABSDIFF_E6], s.absdiff_e6);
-}
 
 // ---------------------------------------------------------------------------------------
 // Launch kernel.  Wave w of workgroup b streams tiles b * kWaves + w + k * tstride with a
@@ -315,12 +276,32 @@ extern "C" int ccfd_score_launch_shadow(const ccfd_shadow_args* sa, void* stream
   }
   const ccfd_score_args& a = sa->base;
   if (a.n < 0) { set_error("n < 0"); return -1; }
-  if (a.model != CCFD_MODEL_MLP) { set_error("shadow launch: champion and shadow must both be MLPs (model kind refused)"); return -3; }
-  if (!(a.flags & CCFD_ARG_WIRE_W64) || (a.flags & (CCFD_ARG_WIRE_G32 | CCFD_ARG_WIRE_G20))) {
-    set_error("shadow launch: W64 rows only (f32 / G32 / G20 rows refused)");
+  if (a.rules != nullptr) { set_error("shadow launch: threshold route only (routing rules refused)"); return -3; }
+  if (a.model == CCFD_MODEL_GBDT) {                  // oblivious GBDT pair on binned rows
+    if (!(a.flags & CCFD_ARG_WIRE_G32) || (a.flags & CCFD_ARG_WIRE_W64)) {
+      set_error("shadow launch: a GBDT pair needs G32 / G20 rows (GBDT on f32 rows refused)");
+      return -3;
+    }
+    if (reinterpret_cast<uintptr_t>(a.x) & ((a.flags & CCFD_ARG_WIRE_G20) ? 3 : 15)) {
+      set_error("G32 rows must be 16-byte aligned, G20 rows 4-byte aligned");
+      return -3;
+    }
+    const int rc = launch_gbdt_shadow(*sa, reinterpret_cast<hipStream_t>(stream));
+    if (rc == -2) set_error("shadow launch: GBDT shape refused (trees >= 1, depth 1..8)");
+    else if (rc) set_error("shadow launch: GBDT kernel launch failed");
+    return rc;
+  }
+  if (a.model != CCFD_MODEL_MLP) {
+    set_error(a.model == CCFD_MODEL_LR ? "shadow launch: LR models have no shadow kernel (MLP on W64 rows, GBDT on G32 / G20 rows)"
+              : a.model == CCFD_MODEL_FOREST
+                  ? "shadow launch: forest models have no shadow kernel (MLP on W64 rows, GBDT on G32 / G20 rows)"
+                  : "shadow launch: model kind refused (MLP on W64 rows, GBDT on G32 / G20 rows)");
     return -3;
   }
-  if (a.rules != nullptr) { set_error("shadow launch: threshold route only (routing rules refused)"); return -3; }
+  if (!(a.flags & CCFD_ARG_WIRE_W64) || (a.flags & (CCFD_ARG_WIRE_G32 | CCFD_ARG_WIRE_G20))) {
+    set_error("shadow launch: an MLP pair needs W64 rows (f32 / G32 / G20 rows refused)");
+    return -3;
+  }
   if (reinterpret_cast<uintptr_t>(a.x) & 15) { set_error("W64 rows must be 16-byte aligned"); return -3; }
   if (a.n == 0) return 0;
   const int ntiles = (a.n + kTileRows - 1) / kTileRows;
@@ -339,7 +320,13 @@ extern "C" int ccfd_persist_launch_shadow(const ccfd_persist_shadow_args* sa, in
   if (!sa || !sa->base.ctl || !sa->base.desc || !sa->base.dev || !sa->base.blob || !sa->shadow_blob) return -1;
   const ccfd_persist_args& a = sa->base;
   if (a.ring <= 0 || a.ring > CCFD_PERSIST_MAX_RING || a.items_per_batch <= 0 || grid < 2) return -2;
-  if (a.model != CCFD_MODEL_MLP || !(a.flags & CCFD_ARG_WIRE_W64) || (a.flags & CCFD_ARG_PIPE_ITEMS) || a.rules) return -3;
+  if ((a.flags & CCFD_ARG_PIPE_ITEMS) || a.rules) return -3;
+  if (a.model == CCFD_MODEL_GBDT) {                  // oblivious GBDT pair on binned rows, items of 1 / 2 / 4 chunks a wave
+    if (!(a.flags & CCFD_ARG_WIRE_G32) || (a.flags & CCFD_ARG_WIRE_W64)) return -3;
+    if (a.tiles_per_wave != 1 && a.tiles_per_wave != 2 && a.tiles_per_wave != 4) return -2;
+    return launch_persist_gbdt_shadow(*sa, grid, reinterpret_cast<hipStream_t>(stream));
+  }
+  if (a.model != CCFD_MODEL_MLP || !(a.flags & CCFD_ARG_WIRE_W64)) return -3;
   if (a.tiles_per_wave != 2 && a.tiles_per_wave != 4 && a.tiles_per_wave != 8) return -2;
   hipLaunchKernelGGL(persist_shadow_kernel, dim3(grid), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), *sa);
   return hipGetLastError() == hipSuccess ? 0 : -5;
