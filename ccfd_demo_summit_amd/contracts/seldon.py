@@ -91,6 +91,15 @@ def build_matrix_response(mat, names: Sequence[str], model_name: str) -> dict:
     return {"meta": meta, "data": {"names": list(names), "ndarray": mat.tolist()}}
 
 
+def build_explain_response(phi, base_value: float, proba1, model_name: str = "modelfull") -> dict:
+    """Explain route: one row of per-feature attributions (margin space) per input row."""
+    phi = np.asarray(phi, dtype=np.float64).reshape(-1, N_FEATURES)
+    meta = {"puid": uuid.uuid4().hex, "routing": {}, "requestPath": {model_name: model_name},
+            "tags": {"base_value": float(base_value),
+                     "proba": np.asarray(proba1, dtype=np.float64).reshape(-1).tolist()}}
+    return {"meta": meta, "data": {"names": list(FEATURE_NAMES), "ndarray": phi.tolist()}}
+
+
 def parse_response(body) -> Tuple[np.ndarray, list]:
     if isinstance(body, (bytes, bytearray, str)):
         body = json.loads(body)

@@ -146,6 +146,7 @@ class ObliviousGBDT:
     leaves: np.ndarray   # float32 [T, 2^D]
     base: float = 0.0
     kind: str = "gbdt"
+    cover: Optional[np.ndarray] = None   # float32 [T, 2^D]: background rows per leaf (models/explain.py)
 
     def __post_init__(self):
         self.feat = np.ascontiguousarray(self.feat, np.int32)
@@ -156,6 +157,10 @@ class ObliviousGBDT:
             raise ValueError(f"depth must be in [1,{MAX_DEPTH}]")
         if self.thr.shape != (T, D) or self.leaves.shape != (T, 1 << D):
             raise ValueError("inconsistent tree arrays")
+        if self.cover is not None:
+            self.cover = np.ascontiguousarray(self.cover, np.float32)
+            if self.cover.shape != (T, 1 << D) or not (self.cover >= 0).all():
+                raise ValueError("cover must be [T, 2^D], finite and >= 0")
         if self.feat.min(initial=0) < 0 or self.feat.max(initial=0) >= N_FEATURES:
             raise ValueError("feature index out of range")
 
@@ -203,6 +208,22 @@ class ObliviousGBDT:
         bits = b[:, self.feat] > k[None]
         return (bits.astype(np.int64) << np.arange(self.depth)).sum(-1)
 
+    def fit_cover(self, X: np.ndarray) -> "ObliviousGBDT":
+        """A copy whose ``cover[t, l]`` counts the rows of ``X`` (the background set of the
+        Shapley attributions, models/explain.py) that land in leaf ``l`` of tree ``t``."""
+        X = np.asarray(X, np.float32)
+        T, D = self.feat.shape
+        count = np.zeros(T << D, np.int64)
+        tree_off = (np.arange(T, dtype=np.int64) << D)[None, :]
+        for s in range(0, X.shape[0], 16384):                # [rows, T] at a time, not [n, T, D]
+            Xc = X[s:s + 16384]
+            idx = np.zeros((Xc.shape[0], T), np.int64)
+            for d in range(D):
+                idx |= (Xc[:, self.feat[:, d]] > self.thr[None, :, d]).astype(np.int64) << d
+            count += np.bincount((idx + tree_off).ravel(), minlength=T << D)
+        cover = count.reshape(T, 1 << D).astype(np.float32)
+        return ObliviousGBDT(self.feat.copy(), self.thr.copy(), self.leaves.copy(), self.base, self.kind, cover)
+
     def raw_score(self, X: np.ndarray) -> np.ndarray:
         idx = self.leaf_index(X)
         vals = self.leaves[np.arange(self.n_trees)[None, :], idx]
@@ -226,7 +247,9 @@ class ObliviousGBDT:
         champion's shape for shadow scoring or a hot swap).  Added levels test ``x[0] > NaN``
         -- never true, packed as bin index 255 -- so a row's leaf index keeps its value and the
         original leaves sit in the low ``2^d`` entries; added trees have all-NaN splits and zero
-        leaves.  ``raw_score`` is bit-identical.  A request to shrink raises ``ValueError``."""
+        leaves.  ``raw_score`` is bit-identical.  A request to shrink raises ``ValueError``.
+        ``cover`` goes along: added leaves and trees hold no background rows, except leaf 0 of
+        an added tree, which holds all of them (the attributions do not change)."""
         T, D = self.feat.shape
         T2 = T if n_trees is None else int(n_trees)
         D2 = D if depth is None else int(depth)
@@ -240,7 +263,12 @@ class ObliviousGBDT:
         feat[:T, :D] = self.feat
         thr[:T, :D] = self.thr
         leaves[:T, :1 << D] = self.leaves
-        return ObliviousGBDT(feat, thr, leaves, self.base)
+        cover = None
+        if self.cover is not None:
+            cover = np.zeros((T2, 1 << D2), np.float32)
+            cover[:T, :1 << D] = self.cover
+            cover[T:, 0] = self.cover[0].astype(np.float64).sum() if T else 0.0
+        return ObliviousGBDT(feat, thr, leaves, self.base, cover=cover)
 
     def pack(self, wire: bool = False, bins: Optional[BinSpec] = None) -> bytes:
         """GBT1 blob for f32 rows, or (``bins``) the GBB1 blob for G32 rows of that spec."""
@@ -278,10 +306,14 @@ class ObliviousGBDT:
         return cls(feat.copy(), thr.copy(), leaves.copy(), float(base))
 
     def state_dict(self) -> dict:
-        return {"gbdt.feat": self.feat, "gbdt.thr": self.thr, "gbdt.leaves": self.leaves,
-                "gbdt.base": np.array([self.base], np.float32)}
+        st = {"gbdt.feat": self.feat, "gbdt.thr": self.thr, "gbdt.leaves": self.leaves,
+              "gbdt.base": np.array([self.base], np.float32)}
+        if self.cover is not None:
+            st["gbdt.cover"] = self.cover
+        return st
 
     @classmethod
     def from_state_dict(cls, st: dict) -> "ObliviousGBDT":
         return cls(st["gbdt.feat"], st["gbdt.thr"], st["gbdt.leaves"],
-                   float(np.asarray(st["gbdt.base"]).reshape(-1)[0]))
+                   float(np.asarray(st["gbdt.base"]).reshape(-1)[0]),
+                   cover=st["gbdt.cover"] if "gbdt.cover" in st else None)

@@ -9,6 +9,8 @@ need:
   "border": b, "split_type": "FloatFeature"}``; split ``d`` of a tree sets bit ``d`` of the
   leaf index when ``x[f] > b`` -- exactly ``ObliviousGBDT.leaf_index``;
 * ``oblivious_trees[t].leaf_values``: ``2**depth`` raw values (binary logloss);
+* ``oblivious_trees[t].leaf_weights`` (optional): training rows per leaf -> ``cover``, the
+  background of the Shapley attributions (models/explain.py);
 * ``scale_and_bias``: ``[scale, [bias]]`` -> raw score = scale * sum(leaves) + bias;
 * ``features_info.float_features[i].flat_feature_index``: the input column of float
   feature ``i`` (categorical features are not supported: transactions are 30 floats).
@@ -55,6 +57,8 @@ def from_catboost_json(doc: Union[str, Dict[str, Any]], column_of: Optional[Dict
     feat = np.zeros((T, depth), np.int32)
     thr = np.full((T, depth), np.nan, np.float32)
     leaves = np.zeros((T, 1 << depth), np.float32)
+    cover = np.zeros((T, 1 << depth), np.float32)        # 'leaf_weights', when every tree has them
+    have_cover = True
     for t, tree in enumerate(trees):
         splits = tree.get("splits") or []
         for d, s in enumerate(splits):
@@ -72,6 +76,14 @@ def from_catboost_json(doc: Union[str, Dict[str, Any]], column_of: Optional[Dict
             raise ValueError(f"tree {t}: {vals.size} leaf values for depth {dt} (multi-class models are not supported)")
         # padded levels never fire, so leaf index = its low dt bits: replicate the table
         leaves[t] = np.tile(vals, 1 << (depth - dt)).astype(np.float32)
+        lw = tree.get("leaf_weights")
+        if lw is None:
+            have_cover = False
+        elif have_cover:
+            lw = np.asarray(lw, np.float64).reshape(-1)
+            if lw.size != (1 << dt):
+                raise ValueError(f"tree {t}: {lw.size} leaf weights for depth {dt}")
+            cover[t, :1 << dt] = lw                      # padded levels never fire: the rows stay low
     scale, bias = 1.0, 0.0
     sb = doc.get("scale_and_bias")
     if sb:
@@ -79,7 +91,7 @@ def from_catboost_json(doc: Union[str, Dict[str, Any]], column_of: Optional[Dict
         b = sb[1]
         bias = float(b[0] if isinstance(b, (list, tuple)) else b)
     leaves = (leaves.astype(np.float64) * scale).astype(np.float32)
-    return ObliviousGBDT(feat, thr, leaves, float(bias))
+    return ObliviousGBDT(feat, thr, leaves, float(bias), cover=cover if have_cover else None)
 
 
 def to_catboost_json(model: ObliviousGBDT) -> Dict[str, Any]:

@@ -75,6 +75,11 @@ class GbdtUpdateArgs(C.Structure):       # ccfd_gbdt_update_args
                 ("split_bin", C.c_int32 * GBDT_MAX_SPLITS)]
 
 
+class GbdtExplainArgs(C.Structure):      # ccfd_gbdt_explain_args
+    _fields_ = [("rows", C.c_void_p), ("blob", C.c_void_p), ("phi", C.c_void_p), ("n", C.c_int64),
+                ("blob_bytes", C.c_int64), ("trees", C.c_int32), ("depth", C.c_int32)]
+
+
 class EngineConfig(C.Structure):
     _fields_ = [("device", C.c_int32), ("model", C.c_int32), ("blob", C.c_void_p),
                 ("gbdt_trees", C.c_int32), ("gbdt_depth", C.c_int32), ("threshold", C.c_float),
@@ -150,6 +155,8 @@ def lib() -> C.CDLL:
         L.ccfd_gbdt_hist_launch.restype = C.c_int
         L.ccfd_gbdt_update_launch.argtypes = [C.POINTER(GbdtUpdateArgs), C.c_void_p]
         L.ccfd_gbdt_update_launch.restype = C.c_int
+        L.ccfd_gbdt_explain_launch.argtypes = [C.POINTER(GbdtExplainArgs), C.c_void_p]
+        L.ccfd_gbdt_explain_launch.restype = C.c_int
         L.ccfd_forest_blob_changed.argtypes = [C.c_void_p]
         L.ccfd_forest_blob_changed.restype = None
         L.ccfd_host_alloc.argtypes = [C.c_size_t]

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from ._lib import (ARG_WIRE_G20, ARG_WIRE_G32, ARG_WIRE_W64, BIN_FORMATS, GBDT_MAX_SPLITS, MODEL_IDS, N_COUNTER_SLOTS,
-                   GbdtHistArgs, GbdtUpdateArgs, ScoreArgs, ShadowArgs, check, lib)
+                   GbdtExplainArgs, GbdtHistArgs, GbdtUpdateArgs, ScoreArgs, ShadowArgs, check, lib)
 
 N_FEATURES = 30
 ROW_BYTES = {"f32": 4 * N_FEATURES, "w64": 64, "g32": 32, "g20": 20}
@@ -289,3 +289,53 @@ def gbdt_apply_tree(rows: torch.Tensor, raw: torch.Tensor, leaf_val: torch.Tenso
     s = stream if stream is not None else torch.cuda.current_stream(rows.device)
     check(lib().ccfd_gbdt_update_launch(C.byref(a), C.c_void_p(s.cuda_stream)), "ccfd_gbdt_update_launch")
     return raw, grad, hess
+
+
+# ---------------------------------------------------------------------------- GBDT explanations
+class DeviceExplainer:
+    """The 'GBX1' table of an oblivious GBDT with cover (``ObliviousGBDT.fit_cover``) resident
+    in HBM, for ``explain_gbdt``.  ``bins``: the 8-bit ``BinSpec`` the G32 rows were encoded
+    with (default: the model's own table).  ``base_value + phi.sum(1)`` is the raw score."""
+
+    def __init__(self, model, bins=None, device: torch.device | str | int = "cuda"):
+        from ..models.explain import ExplainTable, base_value
+        if getattr(model, "kind", None) != "gbdt":
+            raise ValueError(f"no explain kernel for model kind {getattr(model, 'kind', None)!r} (oblivious GBDT only)")
+        self.bins = bins if bins is not None else model.bin_spec()
+        packed = ExplainTable.pack(model, self.bins)
+        self.blob = torch.from_numpy(np.frombuffer(packed, np.uint8).copy()).to(device)
+        self.trees, self.depth = model.n_trees, model.depth
+        self.base_value = base_value(model)
+        self.device = self.blob.device
+
+    def explain(self, X: np.ndarray) -> Tuple[np.ndarray, float]:
+        """float32 [n,30] host rows -> (phi float32 [n,30] numpy, base_value)."""
+        X = np.ascontiguousarray(X, np.float32)
+        if X.ndim != 2 or X.shape[1] != N_FEATURES:
+            raise ValueError("X must be float32 [n, 30]")
+        rows = torch.from_numpy(np.ascontiguousarray(self.bins.encode(X))).to(self.device)
+        return explain_gbdt(self, rows).cpu().numpy(), self.base_value
+
+
+def explain_gbdt(ex: DeviceExplainer, rows: torch.Tensor, out: Optional[torch.Tensor] = None,
+                 stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """Exact per-feature Shapley values (margin space) of G32 ``rows`` ([n,32] u8, CUDA) under
+    ``ex``'s model (csrc/kernels/explain_gbdt.hip; definition in docs/EXPLAIN.md): returns
+    ``phi`` float32 ``[n, 30]`` (``out=`` reuses such a tensor).  A row whose stamp differs from
+    the table's gets NaN in all 30 entries; a feature no tree tests gets exactly 0.  The
+    summation order is fixed: two runs give identical bits."""
+    n = _g32_rows(rows)
+    if rows.device != ex.blob.device:
+        raise ValueError("rows must be on the explainer's device")
+    shape = (n, N_FEATURES)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=rows.device)
+    elif not out.is_cuda or out.device != rows.device or out.dtype != torch.float32 or tuple(out.shape) != shape or \
+            not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous CUDA float32 tensor of shape {list(shape)} on the rows' device")
+    a = GbdtExplainArgs()
+    a.rows, a.blob, a.phi = rows.data_ptr(), ex.blob.data_ptr(), out.data_ptr()
+    a.n, a.blob_bytes, a.trees, a.depth = n, ex.blob.numel(), ex.trees, ex.depth
+    s = stream if stream is not None else torch.cuda.current_stream(rows.device)
+    check(lib().ccfd_gbdt_explain_launch(C.byref(a), C.c_void_p(s.cuda_stream)), "ccfd_gbdt_explain_launch")
+    return out

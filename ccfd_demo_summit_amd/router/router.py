@@ -13,6 +13,12 @@ engine (or from the predict() path) and:
 * consumes ``ccd-customer-response`` and signals the waiting fraud process, counting
   ``notifications.incoming{response}`` (README.md:528-530, 569, 605);
 * counts ``notifications.outgoing`` when a fraud process publishes its notification.
+
+With an ``explainer`` (anything with ``explain(X) -> (phi [n,30], base_value)``: a
+``serving.scorers`` scorer of an oblivious GBDT, or ``ops.kernels.DeviceExplainer``) a fraud
+start from ``on_scored`` also carries ``reasons``, the largest positive Shapley attributions of
+the row (docs/EXPLAIN.md).  ``on_flagged``, the engine hot path, receives no feature rows and
+starts its processes without reasons.
 """
 from __future__ import annotations
 
@@ -52,8 +58,11 @@ def standard_columns(rec: np.ndarray, marks: Optional[Dict[int, int]] = None) ->
 
 class Router:
     def __init__(self, rules: RuleSet, processes, metrics: Optional[RouterMetrics] = None,
-                 standard_mode: str = "count", handoff=None):
-        """``handoff``: a router.handoff.KieHandoff -- fraud starts and customer-response
+                 standard_mode: str = "count", handoff=None, explainer=None, reasons: int = 3):
+        """``explainer`` / ``reasons``: fraud starts of ``on_scored`` batches that come with their
+        feature rows ``X`` carry the ``reasons`` largest positive attributions as
+        ``[{"feature": name, "phi": float}]`` (one ``explain`` call a batch).
+        ``handoff``: a router.handoff.KieHandoff -- fraud starts and customer-response
         signals are then enqueued (pooled, retried, never blocking the caller) instead of
         sent synchronously; ``last_handoff_seq`` is the sequence number of the latest one."""
         if standard_mode not in ("count", "process"):
@@ -67,6 +76,8 @@ class Router:
         self.signals_ok = 0
         self.signals_stale = 0
         self.handoff = handoff
+        self.explainer = explainer
+        self.reasons = int(reasons)
         self.last_handoff_seq = -1
         self.standard_started = 0
         # wall-clock ns the current batch of results was collected from the engine (set by the
@@ -89,9 +100,16 @@ class Router:
         self.metrics.tx_incoming.inc(n)
         self.metrics.tx_outgoing.labels(type="fraud").inc(len(fraud_idx))
         self.metrics.tx_outgoing.labels(type="standard").inc(n - len(fraud_idx))
-        for i in fraud_idx:
+        why = None
+        if self.explainer is not None and X is not None and len(fraud_idx):
+            from ..contracts.transaction import FEATURE_NAMES
+            from ..models.explain import top_reasons
+            phi, _base = self.explainer.explain(np.asarray(X, np.float32)[fraud_idx])    # one batch
+            why = [top_reasons(row, FEATURE_NAMES, self.reasons) for row in np.asarray(phi)]
+        for j, i in enumerate(fraud_idx):
             self._start_fraud(int(ids[i]), int(customers[i]) if customers is not None else 0,
-                              float(amounts[i]) if amounts is not None else 0.0, float(proba[i]))
+                              float(amounts[i]) if amounts is not None else 0.0, float(proba[i]),
+                              None if why is None else why[j])
         if self.standard_mode == "process":
             si = np.nonzero(routes != Route.FRAUD)[0]
             if len(si):
@@ -166,9 +184,11 @@ class Router:
                 self.standard_started += len(standard)
         return {"incoming": total_rows, "fraud": nf, "standard": total_rows - nf}
 
-    def _start_fraud(self, tx_id: int, customer: int, amount: float, proba: float) -> None:
-        self.processes.start_fraud({"transaction_id": tx_id, "customer_id": customer,
-                                    "amount": amount, "proba": proba})
+    def _start_fraud(self, tx_id: int, customer: int, amount: float, proba: float, reasons=None) -> None:
+        v = {"transaction_id": tx_id, "customer_id": customer, "amount": amount, "proba": proba}
+        if reasons is not None:
+            v["reasons"] = reasons
+        self.processes.start_fraud(v)
         with self._lock:
             self.fraud_started += 1
 

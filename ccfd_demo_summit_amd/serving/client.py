@@ -22,6 +22,10 @@ class SeldonClient:
     def __init__(self, url: str, endpoint: str = "api/v0.1/predictions", token: Optional[str] = None,
                  timeout_ms: int = 5000, pool_size: int = 5):
         self.url = _url(url, endpoint)
+        # the explain route next to the prediction route: .../predictions -> .../explain
+        head, _, last = endpoint.rstrip("/").rpartition("/")
+        self.explain_url = _url(url, (head + "/" if head else "") + "explain") \
+            if last in ("predictions", "predict") else _url(url, "explain")
         self.token = token
         self.timeout_s = timeout_ms / 1000.0
         self.pool_size = pool_size
@@ -47,6 +51,20 @@ class SeldonClient:
             self._aio = aiohttp.ClientSession(connector=aiohttp.TCPConnector(limit=self.pool_size),
                                               timeout=aiohttp.ClientTimeout(total=self.timeout_s))
         async with self._aio.post(self.url, data=json.dumps(body), headers=self._headers()) as r:
+            r.raise_for_status()
+            return await r.json()
+
+    def explain_sync(self, body: dict) -> dict:
+        r = self._session.post(self.explain_url, data=json.dumps(body), headers=self._headers(),
+                               timeout=self.timeout_s)
+        r.raise_for_status()
+        return r.json()
+
+    async def explain(self, body: dict) -> dict:
+        if self._aio is None or self._aio.closed:
+            self._aio = aiohttp.ClientSession(connector=aiohttp.TCPConnector(limit=self.pool_size),
+                                              timeout=aiohttp.ClientTimeout(total=self.timeout_s))
+        async with self._aio.post(self.explain_url, data=json.dumps(body), headers=self._headers()) as r:
             r.raise_for_status()
             return await r.json()
 

@@ -5,6 +5,8 @@
                     (pageable host input is staged by DMA; results come back pinned).
 
 Both return ``(proba_1 float32[n], route uint8[n])`` with route = proba >= threshold.
+``explain(X)`` (oblivious GBDT with cover only; anything else raises ``ValueError``) returns
+``(phi float32/64 [n,30], base_value)``, the exact Shapley attributions of docs/EXPLAIN.md.
 """
 from __future__ import annotations
 
@@ -25,6 +27,17 @@ class CpuScorer:
         p = self.model.predict_proba(np.asarray(X, np.float32)).astype(np.float32)
         return p, (p >= self.threshold).astype(np.uint8)
 
+    def explain(self, X: np.ndarray) -> Tuple[np.ndarray, float]:
+        _explainable(self.model)
+        from ..models.explain import shapley_oblivious
+        return shapley_oblivious(self.model, np.asarray(X, np.float32))
+
+
+def _explainable(model) -> None:
+    if getattr(model, "kind", None) != "gbdt":
+        raise ValueError(f"model kind {getattr(model, 'kind', None)!r} has no explanation "
+                         "(exact Shapley values exist for the oblivious GBDT only)")
+
 
 class GpuScorer:
     device = "gpu"
@@ -35,6 +48,9 @@ class GpuScorer:
         from ..engine import StreamEngine
         from ..ops.kernels import DeviceModel
         self.threshold = float(threshold)
+        self.model = model
+        self._device_index = device_index
+        self._explainer = None
         self.dm = DeviceModel(model, torch.device("cuda", device_index))
         self.engine = StreamEngine(self.dm, batch=max_batch, depth=depth, streams=1,
                                    input_mode="dma", output_mode="zerocopy", threshold=threshold,
@@ -44,6 +60,16 @@ class GpuScorer:
     def score(self, X: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         with self._lock:
             return self.engine.score(X)
+
+    def explain(self, X: np.ndarray) -> Tuple[np.ndarray, float]:
+        """csrc/kernels/explain_gbdt.hip on the rows binned against the model's own table."""
+        _explainable(self.model)
+        with self._lock:
+            if self._explainer is None:
+                import torch
+                from ..ops.kernels import DeviceExplainer
+                self._explainer = DeviceExplainer(self.model, device=torch.device("cuda", self._device_index))
+            return self._explainer.explain(X)
 
     def close(self):
         self.engine.close()

@@ -6,6 +6,9 @@ Endpoints (port 8000 like ``SELDON_URL=http://modelfull-modelfull:8000``, router
   POST /api/v1.0/predictions   same, newer path
   POST /predict                model-wrapper API (KIE default endpoint, README.md:379); also
                                accepts form field ``json=``
+  POST /api/v0.1/explain, /api/v1.0/explain, /explain
+                               per-feature Shapley values of the same request body (oblivious
+                               GBDT with cover; docs/EXPLAIN.md); 400 for any other model
   GET  /prometheus, /metrics   model gauges + seldon_api_engine_* histograms
   GET  /health/ping, /health/status, /ready, /live
 
@@ -110,6 +113,8 @@ class SeldonServer:
         r = self.app.router
         for path in ("/api/v0.1/predictions", "/api/v1.0/predictions", "/predict", "/api/v0.1/predict"):
             r.add_post(path, self.predict)
+        for path in ("/api/v0.1/explain", "/api/v1.0/explain", "/explain"):
+            r.add_post(path, self.explain)
         r.add_get("/prometheus", self.prometheus)
         r.add_get("/metrics", self.prometheus)
         for path in ("/health/ping", "/ping", "/live", "/ready", "/health/status"):
@@ -164,6 +169,26 @@ class SeldonServer:
             self.metrics.set_last(X[-1], float(proba[-1]))
         self.metrics.observe_request(time.perf_counter() - t0, 200, model_dt)
         return web.json_response(resp)
+
+    async def explain(self, request: web.Request) -> web.Response:
+        """Seldon data format: ``names`` = FEATURE_NAMES, one phi row per input row (margin
+        space), ``meta.tags`` = {"base_value", "proba"}; base_value + sum(phi) is the log-odds."""
+        if not self._authorized(request):
+            return web.json_response(seldon.error_response(401, "unauthorized"), status=401)
+        try:
+            body = await self._body(request)
+            X, _names = seldon.parse_request(body)
+            if X.shape[1] != 30:
+                raise seldon.SeldonError("expected 30 features")
+            fn = getattr(self.scorer, "explain", None)
+            if fn is None:
+                raise seldon.SeldonError("this model has no explanation")
+            loop = asyncio.get_running_loop()
+            phi, base_value = await loop.run_in_executor(None, fn, X)
+            proba, _ = await loop.run_in_executor(None, self.scorer.score, X)
+        except (seldon.SeldonError, json.JSONDecodeError, ValueError, KeyError) as e:
+            return web.json_response(seldon.error_response(400, str(e)), status=400)
+        return web.json_response(seldon.build_explain_response(phi, base_value, proba, self.model_name))
 
     async def prometheus(self, _request: web.Request) -> web.Response:
         return web.Response(body=self.metrics.expose(), headers={"Content-Type": CONTENT_TYPE})

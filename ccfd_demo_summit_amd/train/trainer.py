@@ -281,6 +281,23 @@ def _boost_hip(rows: torch.Tensor, yt: torch.Tensor, raw: torch.Tensor, borders:
         gbdt_apply_tree(rows, raw, vals, splits, y=yt, grad=grad, hess=hess)
 
 
+def _leaf_counts(X: np.ndarray, feat: np.ndarray, thr: np.ndarray, dev) -> torch.Tensor:
+    """``ObliviousGBDT.fit_cover`` on the training device: rows of X per (tree, leaf), float64
+    [T, 2^D] (a sum the ranks all-reduce)."""
+    T, D = feat.shape
+    ft = torch.from_numpy(feat.astype(np.int64)).to(dev)
+    tt = torch.from_numpy(np.ascontiguousarray(thr, np.float32)).to(dev)
+    shift = torch.arange(D, device=dev)
+    tree_off = torch.arange(T, device=dev) << D
+    count = torch.zeros(T << D, dtype=torch.float64, device=dev)
+    step = max(1, (1 << 22) // (T * D))                               # ~4 M compares at a time
+    for s in range(0, X.shape[0], step):
+        Xc = torch.from_numpy(np.ascontiguousarray(X[s:s + step], np.float32)).to(dev)
+        idx = ((Xc[:, ft] > tt).long() << shift).sum(-1) + tree_off    # [rows, T]
+        count += torch.bincount(idx.reshape(-1), minlength=T << D)
+    return count.view(T, 1 << D)
+
+
 def train_oblivious_gbdt(X: np.ndarray, y: np.ndarray, n_trees: int = 100, depth: int = 6,
                          learning_rate: float = 0.1, n_bins: int = 32, l2: float = 1.0,
                          device: str = "auto", borders: Optional[np.ndarray] = None,
@@ -419,6 +436,9 @@ def train_oblivious_gbdt(X: np.ndarray, y: np.ndarray, n_trees: int = 100, depth
         leaves[t] = vals.cpu().numpy()
         raw = raw + vals[leaf]
     model = ObliviousGBDT(feat, thr, leaves, float(base))
+    # background of the Shapley attributions (models/explain.py): the training rows per leaf,
+    # summed over the ranks' shards
+    model.cover = allreduce(_leaf_counts(X, feat, thr, dev)).cpu().numpy().astype(np.float32)
     with torch.no_grad():
         ll_sum = torch.nn.functional.binary_cross_entropy_with_logits(raw, yt, reduction="sum").double()
         ll = float(allreduce(ll_sum.reshape(1))[0]) / max(float(stats[1]), 1.0)

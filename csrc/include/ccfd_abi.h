@@ -211,6 +211,28 @@ typedef struct ccfd_gbdt_update_args {
 int ccfd_gbdt_update_launch(const ccfd_gbdt_update_args* a, void* stream);
 
 // ---------------------------------------------------------------------------
+// Exact per-feature Shapley values of an oblivious GBDT on G32 rows (explain_gbdt.hip;
+// models/explain.py holds the definition, the CPU oracle and the packer of the 'GBX1' blob).
+// phi[i][j] is the attribution of feature j to the margin (log-odds) of row i; the blob's
+// base_value + sum_j phi[i][j] is the row's raw score.  A row whose stamp (byte 31) differs from
+// the blob's gets quiet NaN in all 30 outputs.  `trees` / `depth` / `blob_bytes` describe the
+// blob the caller packed (the launch cannot read device memory): trees >= 1, depth 1..8,
+// blob_bytes >= the GBX1 size of that shape.  n >= 0; n == 0 returns without a launch.  A plain
+// grid launch on `stream`; the summation order is fixed, so results are bit-reproducible.
+#define CCFD_GBX_META_WORDS 48
+#define CCFD_GBX_WEIGHT_BYTES (9 * 8 * 8)
+typedef struct ccfd_gbdt_explain_args {
+  const uint8_t* rows;   // device [n][32], 16-byte aligned
+  const void* blob;      // device GBX1 blob, 16-byte aligned
+  float* phi;            // device out [n][30]
+  int64_t n;
+  int64_t blob_bytes;
+  int32_t trees;
+  int32_t depth;
+} ccfd_gbdt_explain_args;   // 48 bytes
+int ccfd_gbdt_explain_launch(const ccfd_gbdt_explain_args* a, void* stream);
+
+// ---------------------------------------------------------------------------
 // Persistent streaming kernel (exec_mode = 1): ONE long-running launch per engine; the
 // host publishes micro-batch descriptors into a ring in coherent pinned memory and bumps
 // `posted`; resident workgroups claim 64..256-row work items with one device atomic, wait for

@@ -7,7 +7,8 @@ as a script to run, or to paste into a notebook cell by cell (the ``# %%`` marke
 3. compare them on a held-out split (ROC-AUC, PR-AUC);
 4. check that the GBDT's exact 32-byte G32 wire picks the f32 model's leaves;
 5. save versioned safetensors files a running engine hot-swaps (``launch engine --watch-model``);
-6. with an MI355X visible, score through the HIP kernels and compare with the CPU models.
+6. print the top reasons (exact per-feature Shapley values) of the highest-scoring rows;
+7. with an MI355X visible, score through the HIP kernels and compare with the CPU models.
 
     python examples/model_workbench.py [--csv creditcard.csv] [--rows 200000] [--out models_out]
 
@@ -88,6 +89,23 @@ def main(argv=None) -> dict:
         back = load_model(path)
         assert np.allclose(back.predict_proba(Xte[:1000]), m.predict_proba(Xte[:1000]), atol=1e-6)
         print("saved", path)
+
+    # %% why were the highest-scoring rows flagged?  (exact Shapley values, docs/EXPLAIN.md)
+    from ccfd_demo_summit_amd.contracts.transaction import FEATURE_NAMES
+    from ccfd_demo_summit_amd.models.explain import shapley_oblivious, top_reasons
+    top = np.argsort(-gb.predict_proba(Xte))[:3]
+    on_gpu = torch.cuda.is_available() and device.startswith("cuda")
+    if on_gpu:
+        from ccfd_demo_summit_amd.ops.kernels import DeviceExplainer
+        phi, base_value = DeviceExplainer(gb, bins=spec, device=torch.device(device)).explain(Xte[top])
+    else:
+        phi, base_value = shapley_oblivious(gb, Xte[top])
+    report["reasons"] = {"base_value": float(base_value), "backend": "hip" if on_gpu else "cpu", "rows": []}
+    for i, row in zip(top, phi):
+        why = top_reasons(row, FEATURE_NAMES, 3)
+        report["reasons"]["rows"].append({"row": int(i), "raw_score": float(base_value + row.sum()), "reasons": why})
+        print(f"row {int(i)}: log-odds {base_value + row.sum():+.3f} = base {base_value:+.3f} "
+              + " ".join(f"{w['feature']} {w['phi']:+.3f}" for w in why) + " ...")
 
     # %% score through the MI355X kernels
     if torch.cuda.is_available() and device.startswith("cuda"):
