@@ -99,6 +99,8 @@ class EngineConfig:
                                      # one per partition for GBDT's binned rows, else 1)
     model_watch: str = ""            # hot-swap when this safetensors file changes (rank 0)
     shadow_model: str = ""           # challenger (safetensors MLP, or GBDT on binned rows) scored beside the live model, counters only
+    drift_reference: str = ""        # drift reference (safetensors, train --drift-reference-out): every ingested row is
+                                     # counted against it, ccfd_gpu_drift_* series (Python ingest, launch mode, G32 / G20)
     output_mode: str = "zerocopy"    # zerocopy (kernel writes pinned host) | dma
     exec_mode: str = "auto"          # persistent | launch | auto (persistent for zero-copy in/out:
                                      # the mode bench.py measures; launch_/engine_service.py)
@@ -154,6 +156,7 @@ ENV_MAP = {
     "CCFD_COALESCE": ("engine", "coalesce", int),
     "CCFD_MODEL_WATCH": ("engine", "model_watch", str),
     "CCFD_SHADOW_MODEL": ("engine", "shadow_model", str),
+    "CCFD_DRIFT_REFERENCE": ("engine", "drift_reference", str),
     "CCFD_INPUT_MODE": ("engine", "input_mode", str),
     "CCFD_OUTPUT_MODE": ("engine", "output_mode", str),
     "CCFD_EXEC_MODE": ("engine", "exec_mode", str),

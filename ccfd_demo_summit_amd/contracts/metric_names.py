@@ -38,6 +38,11 @@ GPU_TX_PER_SEC = GPU_PREFIX + "tx_per_second"        # gauge
 GPU_INFLIGHT = GPU_PREFIX + "inflight_batches"       # gauge
 GPU_GLOBAL_FRAUD_RATE = GPU_PREFIX + "global_fraud_rate"  # gauge (all-reduced)
 GPU_AMOUNT = GPU_PREFIX + "amount"                   # histogram{type} (device-side)
+# feature drift of the ingested rows against the training reference (docs/DRIFT.md)
+GPU_DRIFT_PSI = GPU_PREFIX + "drift_psi"             # gauge{feature}: PSI of the open window
+GPU_DRIFT_ROWS = GPU_PREFIX + "drift_rows"           # counter (_total): rows counted in the window
+GPU_DRIFT_STALE_ROWS = GPU_PREFIX + "drift_stale_rows"    # counter (_total): rows of another bin table
+GPU_DRIFT_FEATURES_DRIFTING = GPU_PREFIX + "drift_features_drifting"   # gauge: columns with status "drift"
 
 ROUTER_METRICS = (TRANSACTION_INCOMING, TRANSACTION_OUTGOING, NOTIFICATIONS_OUTGOING,
                   NOTIFICATIONS_INCOMING)

@@ -97,6 +97,11 @@ def encode_g32(X: np.ndarray, bins, out_ptr: int, amount_ptr: Optional[int] = No
 encode_bins = encode_g32
 
 
+def _ring_view(log, r: int, k: int) -> np.ndarray:
+    """Rows [r, r + k) of a partition log as they lie in memory: uint8 [k, row_bytes]."""
+    return log.feats.array.view(np.uint8).reshape(-1, log.row_bytes)[r:r + k]
+
+
 class PartitionLog:
     """One Kafka-partition-like append log of transactions in pinned host memory.
 
@@ -676,9 +681,12 @@ class StreamEngine:
         return log
 
     def ring_write(self, partition: int, X: np.ndarray, ids: Optional[np.ndarray] = None,
-                   customer: Optional[np.ndarray] = None, block: bool = True) -> int:
+                   customer: Optional[np.ndarray] = None, block: bool = True, tap=None) -> int:
         """Producer side: append rows (copied into the pinned ring, wrapping as needed).
-        Returns rows written (< len(X) only when ``block`` is False and the ring is full)."""
+        Returns rows written (< len(X) only when ``block`` is False and the ring is full).
+        ``tap(view)`` is called with the just-encoded ``uint8 [k, row_bytes]`` slice of the ring
+        before it is committed: the producer still owns those slots, so the tap may read them
+        without racing the consumer (``DriftMonitor.observe_host`` copies them)."""
         log = self.logs[partition]
         n = X.shape[0]
         done = 0
@@ -699,12 +707,15 @@ class StreamEngine:
                 log.ids.array[r:r + k] = ids[done:done + k]
             if customer is not None:
                 log.customer.array[r:r + k] = customer[done:done + k]
+            if tap is not None:
+                tap(_ring_view(log, r, k))
             lib().ccfd_engine_ring_commit(C.c_void_p(self.h), int(partition), k)
             done += k
         return done
 
-    def ring_write_json(self, partition: int, values) -> int:
-        """Parse JSON transaction messages with the native parser straight into the ring."""
+    def ring_write_json(self, partition: int, values, tap=None) -> int:
+        """Parse JSON transaction messages with the native parser straight into the ring.
+        ``tap``: as in ``ring_write``."""
         log = self.logs[partition]
         n = len(values)
         done = 0
@@ -733,6 +744,8 @@ class StreamEngine:
                             log.ids.ptr + r * 8, log.customer.ptr + r * 4)
             if got != k:
                 raise ValueError(f"malformed transaction message #{done - got - 1}")
+            if tap is not None:
+                tap(_ring_view(log, r, k))
             L.ccfd_engine_ring_commit(C.c_void_p(self.h), int(partition), k)
             done += k
         return done

@@ -176,11 +176,21 @@ def cmd_kafka_controller(a, cfg):
     main(argv)
 
 
+def _set_drift(scorer, a) -> None:
+    """--drift-reference: count every scored batch against the reference (the /drift routes)."""
+    path = getattr(a, "drift_reference", None)
+    if path:
+        from ..models.drift import DriftReference
+        scorer.set_drift(DriftReference.load(path))
+        print(f"[drift] reference {path}: GET /drift reports PSI per feature", flush=True)
+
+
 def cmd_seldon(a, cfg):
     from ..serving.scorers import make_scorer
     from ..serving.seldon_server import SeldonServer, run
     model = _model(cfg.engine.model, a.weights, cfg.seed)
     scorer = make_scorer(model, cfg.router.fraud_threshold, device=a.device, max_batch=cfg.seldon.max_batch)
+    _set_drift(scorer, a)
     if a.native:
         # C++ epoll front end (csrc/engine/seldon_http.cpp): same routes, JSON and metrics
         from ..serving.native_seldon import NativeSeldonServer
@@ -373,7 +383,8 @@ def engine_service_settings(a, cfg):
         standard_mode=cfg.router.standard_mode, scored_capacity=cfg.engine.scored_capacity,
         native_serve=cfg.engine.native_serve,
         model_watch=(a.watch_model or cfg.engine.model_watch or None),
-        shadow_model=(a.shadow_model or cfg.engine.shadow_model or None))
+        shadow_model=(a.shadow_model or cfg.engine.shadow_model or None),
+        drift_reference=(getattr(a, "drift_reference", None) or cfg.engine.drift_reference or None))
 
 
 def cmd_engine(a, cfg):
@@ -427,7 +438,14 @@ def cmd_engine(a, cfg):
                                  cfg.engine.model, dm.row_format, bins=getattr(dm, "bins", None))
         print(f"[engine] shadow model {settings.shadow_model}: scored beside the live model, counters only",
               flush=True)
-    svc = EngineService(ctx, dm, broker, router, settings, shadow=shadow).start()
+    drift = None
+    if settings.drift_reference:
+        # every rank counts the rows it ingests against the same reference; the series are per rank
+        from ..models.drift import DriftReference
+        from ..ops.kernels import DriftMonitor
+        drift = DriftMonitor(DriftReference.load(settings.drift_reference), ctx.device)
+        print(f"[engine] drift reference {settings.drift_reference}: ccfd_gpu_drift_* series", flush=True)
+    svc = EngineService(ctx, dm, broker, router, settings, shadow=shadow, drift=drift).start()
     hub.gpu_registry.register(GpuEngineCollector(svc.metrics_source, rank_label=str(ctx.rank)))
     # the process's node-local rank (torchrun LOCAL_RANK) -- not the device index, which a
     # several-ranks-per-GPU rehearsal (CCFD_DEVICE_MODULO) maps onto the same GPU
@@ -546,6 +564,7 @@ def cmd_demo(a, cfg):
     from ..serving.scorers import make_scorer
     model = _model(cfg.engine.model, a.weights, cfg.seed)
     scorer = make_scorer(model, cfg.router.fraud_threshold, device=a.device)
+    _set_drift(scorer, a)
     pipe = FraudPipeline(cfg, scorer, InProcBroker(default_partitions=cfg.kafka.partitions))
     _serve_in_thread(_metrics_app(pipe.metrics.expose_all), a.host, a.port or cfg.router.port)
     prod = TransactionProducer(pipe.broker, ProducerConfig(fmt=a.fmt, batch=a.batch, rate_tx_s=a.rate))
@@ -555,8 +574,10 @@ def cmd_demo(a, cfg):
         pipe.step()
     pipe.run_until_idle(1000)
     oc = pipe.processes.outcome_counts
-    print(json.dumps({"consumed": pipe.stats.consumed, "outcomes": oc,
-                      "scorer": getattr(scorer, "device", "cpu")}), flush=True)
+    out = {"consumed": pipe.stats.consumed, "outcomes": oc, "scorer": getattr(scorer, "device", "cpu")}
+    if getattr(a, "drift_reference", None):
+        out["drift"] = scorer.drift().to_json()
+    print(json.dumps(out), flush=True)
 
 
 def cmd_store(a, cfg):
@@ -721,6 +742,10 @@ def parse_args(argv=None) -> argparse.Namespace:
                          "GBDT on G32 / G20 rows (packed against the live bin table; train it with "
                          "`train --bin-spec-from`) "
                          "(shadow counters and ccfd_gpu_shadow_* series only; promote it with --watch-model)")
+    ap.add_argument("--drift-reference", default=None,
+                    help="seldon/engine/demo: drift reference (train --drift-reference-out) the scored / ingested rows "
+                         "are counted against: GET /drift on the Seldon server, ccfd_gpu_drift_* series on the engine "
+                         "(Python ingest, exec_mode launch, G32 / G20 rows)")
     ap.add_argument("--model-metrics-port", type=int, default=None,
                     help="engine: port (+ local rank) of the model's /prometheus (proba_1 / Amount / V17 / V10, "
                          "seldon_api_engine_*); default SELDON port 8000, 0 = off")

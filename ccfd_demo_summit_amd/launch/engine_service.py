@@ -29,6 +29,7 @@ from typing import Deque, Dict, List, Optional, Tuple
 
 import numpy as np
 
+from ..contracts import metric_names as M
 from ..contracts.transaction import TXB_MAGIC, TxBatch
 from ..ops._lib import FLAGGED_DTYPE
 
@@ -74,6 +75,8 @@ class EngineServiceConfig:
                                      # for the GIL between run() calls (profiles/r4/tail/)
     serve_budget_us: int = 200       # native serving thread: run() budget per iteration
     model_watch: Optional[str] = None   # rank 0: hot-swap when this safetensors file changes
+    drift_reference: Optional[str] = None  # file the drift reference was loaded from; the monitor
+                                           # itself is EngineService(drift=)
     shadow_model: Optional[str] = None  # file the shadow (challenger) model was loaded from; the
                                         # packed model itself is EngineService(shadow=)
     handoff_hold_low: float = 0.5    # a held (full) hand-off queue resumes scoring below this fill
@@ -112,13 +115,34 @@ def resolve_exec_mode(exec_mode: str, model_kind: str, row_format: str, input_mo
     return "persistent" if zc and ok else "launch"
 
 
+def check_drift_tap(drift, dm, exec_mode: str, native_ingest: bool) -> None:
+    """Refuse (``ValueError`` naming the reason) every engine a ``DriftMonitor`` cannot tap: the
+    tap is the Python ingest path's ``ring_write(tap=)``, over G32 / G20 rows of the reference's
+    own table, beside per-batch launches.  Pure host check."""
+    if native_ingest:
+        raise ValueError("drift monitor: the native Kafka consumer writes the rings from C++ and has no tap; "
+                         "use the in-process broker or native_ingest=False")
+    fmt = dm.row_format
+    if fmt not in ("g32", "g20"):
+        raise ValueError(f"drift monitor: the engine's rows are {fmt}, not binned (G32 / G20: a GBDT packed with bins=)")
+    if exec_mode != "launch":
+        raise ValueError(f"drift monitor: exec_mode is {exec_mode!r}; a second kernel beside the persistent one is "
+                         "not supported, use exec_mode=\"launch\"")
+    ref = drift.reference
+    if not ref.compatible(dm.bins):
+        raise ValueError(f"drift monitor: the reference (stamp {ref.stamp}, {ref.bits}-bit) was not counted against "
+                         f"the engine's bin table (stamp {dm.bins.stamp}, {dm.bins.bits}-bit)")
+
+
 class EngineService:
     def __init__(self, ctx, dm, broker, router, cfg: EngineServiceConfig, reducer=None, partitions=None,
-                 shadow=None):
+                 shadow=None, drift=None):
         """``shadow``: a challenger DeviceModel (an MLP on W64 rows, or a GBDT of ``dm``'s shape
         packed against ``dm``'s G32 / G20 bin table) scored beside ``dm`` from the
         first micro-batch on; its results are the shadow counter slots of the X2 all-reduce and
-        the ``ccfd_gpu_shadow_*`` series (engine.StreamEngine.set_shadow)."""
+        the ``ccfd_gpu_shadow_*`` series (engine.StreamEngine.set_shadow).
+        ``drift``: an ``ops.kernels.DriftMonitor`` fed every ingested row (``ring_write(tap=)``)
+        and reported as the ``ccfd_gpu_drift_*`` series; ``check_drift_tap`` lists what is refused."""
         from ..engine import StreamEngine
         from ..parallel.dp import CounterReducer, EpochPipeline, assign_partitions, x_group
         self.ctx = ctx
@@ -139,6 +163,12 @@ class EngineService:
                 from ..ops.kernels import DeviceRules
                 self.device_rules = DeviceRules(rules, ctx.device)
         self.exec_mode = resolve_exec_mode(cfg.exec_mode, dm.kind, dm.row_format, cfg.input_mode, cfg.output_mode)
+        self.drift = drift
+        self._drift_report = None
+        self._tap = None
+        if drift is not None:
+            check_drift_tap(drift, dm, self.exec_mode, bool(cfg.native_ingest and hasattr(broker, "_bootstrap")))
+            self._tap = drift.observe_host
         self.engine = StreamEngine(dm, batch=cfg.batch, depth=cfg.depth, streams=cfg.streams,
                                    input_mode=cfg.input_mode, output_mode=cfg.output_mode, threshold=threshold,
                                    device=ctx.device.index, exec_mode=self.exec_mode, coalesce=cfg.coalesce,
@@ -272,7 +302,7 @@ class EngineService:
                         self._pending[p].append((self._rows_in[p], last_off + 1))
                         json_run = []
                     b = TxBatch.decode(r.value)
-                    k = self.engine.ring_write(p, b.features, b.ids, b.customer)
+                    k = self.engine.ring_write(p, b.features, b.ids, b.customer, tap=self._tap)
                     self._rows_in[p] += k
                     n += k
                     self._pending[p].append((self._rows_in[p], r.offset + 1))
@@ -288,7 +318,7 @@ class EngineService:
         return n
 
     def _write_json(self, p: int, values: List[bytes]) -> int:
-        k = self.engine.ring_write_json(p, values)
+        k = self.engine.ring_write_json(p, values, tap=self._tap)
         self._rows_in[p] += k
         return k
 
@@ -480,8 +510,14 @@ class EngineService:
         if ok:
             self._lat_prev = lat_cum
         self.hotswap.poll()                             # runtime X1: swap once the blob landed
+        self.refresh_drift()
         self._reduce_pending = False
         return ok
+
+    def refresh_drift(self) -> None:
+        """Read the drift window back (epoch cadence, never per batch) for ``metrics_source``."""
+        if self.drift is not None:
+            self._drift_report = self.drift.report()
 
     def _score_loop(self) -> None:
         try:
@@ -614,6 +650,7 @@ class EngineService:
                     self._reduce(lat, block=True)
             self.epochs.finish(progress=self._progress)
             self.hotswap.poll(block=True)
+            self.refresh_drift()
         self._on_engine_thread(_do)
 
     def latency_hist(self) -> np.ndarray:
@@ -711,6 +748,15 @@ class EngineService:
                 if h.count():                           # scored -> started, the engine's share
                     extra[f"handoff_{key}_p50_seconds"] = h.quantile_ns(0.5) * 1e-9
                     extra[f"handoff_{key}_p99_seconds"] = h.quantile_ns(0.99) * 1e-9
+        rep = self._drift_report
+        if rep is not None:
+            # a window too short for PSI (DriftReport min_rows) publishes its row counts only
+            extra[M.GPU_DRIFT_ROWS + "_total"] = rep.rows
+            extra[M.GPU_DRIFT_STALE_ROWS + "_total"] = rep.stale
+            if rep.rows >= rep.min_rows:
+                cut = len(M.GPU_PREFIX)                  # gauges get the prefix back in the collector
+                extra[M.GPU_DRIFT_PSI[cut:]] = {"feature": dict(zip(rep.names, rep.psi.tolist()))}
+                extra[M.GPU_DRIFT_FEATURES_DRIFTING[cut:]] = rep.drifting
         if self.standard_mode == "process":
             extra.update(standard_started=getattr(self.router, "standard_started", 0))
         with self._stat_lock:

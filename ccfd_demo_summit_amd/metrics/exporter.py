@@ -299,6 +299,13 @@ class GpuEngineCollector:
                 q.add_metric([str(qq)], hist_quantile(lat, qq) * 1e-9)
             yield q
         for k, v in (extra or {}).items():
+            if isinstance(v, dict):                     # {label: {value: x}}: one labelled gauge,
+                (label, series), = v.items()            # e.g. drift_psi{feature=...}
+                g = GaugeMetricFamily(M.GPU_PREFIX + k, k, labels=[label])
+                for lv, x in series.items():
+                    g.add_metric([str(lv)], float(x))
+                yield g
+                continue
             if k.endswith("_total"):                    # counters keep their own name, e.g.
                 c = CounterMetricFamily(k[:-len("_total")], k)    # handoff_dead_letter_total
                 c.add_metric([], float(v))

@@ -80,6 +80,14 @@ class GbdtExplainArgs(C.Structure):      # ccfd_gbdt_explain_args
                 ("blob_bytes", C.c_int64), ("trees", C.c_int32), ("depth", C.c_int32)]
 
 
+DRIFT_COLS, DRIFT_CELLS = 31, 256       # ccfd_abi.h CCFD_DRIFT_*
+
+
+class DriftHistArgs(C.Structure):        # ccfd_drift_hist_args
+    _fields_ = [("rows", C.c_void_p), ("counts", C.c_void_p), ("tail", C.c_void_p), ("n", C.c_int64),
+                ("wire", C.c_int32), ("stamp", C.c_int32), ("max_workgroups", C.c_int32), ("pad", C.c_int32)]
+
+
 class EngineConfig(C.Structure):
     _fields_ = [("device", C.c_int32), ("model", C.c_int32), ("blob", C.c_void_p),
                 ("gbdt_trees", C.c_int32), ("gbdt_depth", C.c_int32), ("threshold", C.c_float),
@@ -157,6 +165,8 @@ def lib() -> C.CDLL:
         L.ccfd_gbdt_update_launch.restype = C.c_int
         L.ccfd_gbdt_explain_launch.argtypes = [C.POINTER(GbdtExplainArgs), C.c_void_p]
         L.ccfd_gbdt_explain_launch.restype = C.c_int
+        L.ccfd_drift_hist_launch.argtypes = [C.POINTER(DriftHistArgs), C.c_void_p]
+        L.ccfd_drift_hist_launch.restype = C.c_int
         L.ccfd_forest_blob_changed.argtypes = [C.c_void_p]
         L.ccfd_forest_blob_changed.restype = None
         L.ccfd_host_alloc.argtypes = [C.c_size_t]

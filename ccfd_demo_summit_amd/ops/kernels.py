@@ -7,13 +7,15 @@ the gfx950 code object or raise (the CPU oracles live in ``models/*.py``).
 from __future__ import annotations
 
 import ctypes as C
+import threading
 from typing import Optional, Tuple
 
 import numpy as np
 import torch
 
-from ._lib import (ARG_WIRE_G20, ARG_WIRE_G32, ARG_WIRE_W64, BIN_FORMATS, GBDT_MAX_SPLITS, MODEL_IDS, N_COUNTER_SLOTS,
-                   GbdtExplainArgs, GbdtHistArgs, GbdtUpdateArgs, ScoreArgs, ShadowArgs, check, lib)
+from ._lib import (ARG_WIRE_G20, ARG_WIRE_G32, ARG_WIRE_W64, BIN_FORMATS, DRIFT_CELLS, DRIFT_COLS, GBDT_MAX_SPLITS,
+                   MODEL_IDS, N_COUNTER_SLOTS, DriftHistArgs, GbdtExplainArgs, GbdtHistArgs, GbdtUpdateArgs, ScoreArgs,
+                   ShadowArgs, check, lib)
 
 N_FEATURES = 30
 ROW_BYTES = {"f32": 4 * N_FEATURES, "w64": 64, "g32": 32, "g20": 20}
@@ -339,3 +341,141 @@ def explain_gbdt(ex: DeviceExplainer, rows: torch.Tensor, out: Optional[torch.Te
     s = stream if stream is not None else torch.cuda.current_stream(rows.device)
     check(lib().ccfd_gbdt_explain_launch(C.byref(a), C.c_void_p(s.cuda_stream)), "ccfd_gbdt_explain_launch")
     return out
+
+
+# ---------------------------------------------------------------------------- feature drift
+_DRIFT_FMT = {ROW_BYTES["g32"]: "g32", ROW_BYTES["g20"]: "g20"}
+DRIFT_STAGE_ROWS = 65536        # rows of one pinned staging buffer of DriftMonitor.observe_host
+
+
+def new_drift_counts(device="cuda") -> Tuple[torch.Tensor, torch.Tensor]:
+    """Zeroed ``(counts uint64 [31,256], tail uint64 [2])`` for ``drift_histogram``."""
+    return (torch.zeros((DRIFT_COLS, DRIFT_CELLS), dtype=torch.int64, device=device).view(torch.uint64),
+            torch.zeros(2, dtype=torch.int64, device=device).view(torch.uint64))
+
+
+def _drift_launch(ptr: int, n: int, fmt: str, stamp: int, counts: torch.Tensor, tail: torch.Tensor,
+                  max_workgroups: int, stream: torch.cuda.Stream) -> None:
+    a = DriftHistArgs()
+    a.rows, a.counts, a.tail = ptr, counts.data_ptr(), tail.data_ptr()
+    a.n, a.wire, a.stamp, a.max_workgroups = int(n), WIRE_FLAGS[fmt], int(stamp), int(max_workgroups)
+    check(lib().ccfd_drift_hist_launch(C.byref(a), C.c_void_p(stream.cuda_stream)), "ccfd_drift_hist_launch")
+
+
+def drift_histogram(rows: torch.Tensor, stamp: int, counts: Optional[torch.Tensor] = None,
+                    tail: Optional[torch.Tensor] = None, max_workgroups: int = 512,
+                    stream: Optional[torch.cuda.Stream] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-feature bin counts of binned rows (csrc/kernels/drift_hist.hip; oracle
+    ``models.drift.bin_counts``).  ``rows``: contiguous CUDA uint8 ``[n,32]`` (G32) or ``[n,20]``
+    (G20); the format follows from the width.  For every row whose stamp equals ``stamp``:
+    ``counts[j, bin_j] += 1`` for j < 30, ``counts[30, amount bucket] += 1`` and ``tail[0] += 1``;
+    a row with another stamp adds 1 to ``tail[1]`` and nothing else.  G20 rows only touch cells
+    0..31 of a column.  Returns ``(counts uint64 [31,256], tail uint64 [2])``.  Missing outputs are
+    allocated zeroed; given ones are ACCUMULATED into (the launch never zeroes), so a window is
+    whatever was summed since the caller last zeroed them.  Integer sums: exact, identical from
+    run to run and for every ``max_workgroups`` (the upper bound on the grid).  ``n == 0``
+    launches nothing; a stamp outside 1..255 (G20: 1..63), G32 rows off a 16-byte boundary or
+    G20 rows off a 4-byte one are refused by the library (``RuntimeError`` with its message)."""
+    if not rows.is_cuda or rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] not in _DRIFT_FMT or \
+            not rows.is_contiguous():
+        raise ValueError("rows must be contiguous CUDA G32 / G20 rows ([n,32] or [n,20] u8)")
+    if counts is None or tail is None:
+        fresh = new_drift_counts(rows.device)
+        counts = fresh[0] if counts is None else counts
+        tail = fresh[1] if tail is None else tail
+    for name, t, shape in (("counts", counts, (DRIFT_COLS, DRIFT_CELLS)), ("tail", tail, (2,))):
+        if not t.is_cuda or t.device != rows.device or t.dtype != torch.uint64 or tuple(t.shape) != shape or \
+                not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous CUDA uint64 tensor of shape {list(shape)} on the rows' device")
+    s = stream if stream is not None else torch.cuda.current_stream(rows.device)
+    _drift_launch(rows.data_ptr(), rows.shape[0], _DRIFT_FMT[rows.shape[1]], stamp, counts, tail, max_workgroups, s)
+    return counts, tail
+
+
+class DriftMonitor:
+    """A tumbling window of bin counts on the GPU, compared against a ``models.drift.DriftReference``.
+
+    ``observe(rows)`` counts CUDA rows on the caller's current stream; ``observe_host(rows)``
+    copies a host ``uint8 [k, row_bytes]`` view into one of two pinned staging buffers and counts
+    it from there on the monitor's own stream (the kernel reads the pinned memory directly, as
+    the engines read their logs), so the caller's memory is free again when it returns.
+    ``report()`` reads the counts back and computes PSI on the host.  Thread-safe (one lock)."""
+
+    def __init__(self, reference, device: torch.device | str | int = "cuda", max_workgroups: int = 512,
+                 min_rows: int = 10_000, bands=(0.1, 0.25)):
+        from ..engine.stream_engine import PinnedArray
+        self.reference = reference
+        self.fmt = "g32" if reference.bits == 8 else "g20"
+        self.row_bytes = ROW_BYTES[self.fmt]
+        self.device = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.max_workgroups, self.min_rows, self.bands = int(max_workgroups), int(min_rows), tuple(bands)
+        self.counts, self.tail = new_drift_counts(self.device)
+        with torch.cuda.device(self.device):
+            self._stream = torch.cuda.Stream(self.device)
+            self._stage = [PinnedArray((DRIFT_STAGE_ROWS, self.row_bytes), np.uint8) for _ in range(2)]
+            self._stage_ptr = [int(lib().ccfd_host_device_ptr(C.c_void_p(p.ptr))) for p in self._stage]
+        self._busy: list = [None, None]          # event of the last launch that read each buffer
+        self._next = 0
+        self._streams = {}                       # streams observe() launched on since the last report
+        self._lock = threading.Lock()
+        torch.cuda.current_stream(self.device).synchronize()     # the zeroed outputs, before any side-stream launch
+
+    def _check(self, width: int) -> None:
+        if width != self.row_bytes:
+            raise ValueError(f"drift reference is for {self.fmt} rows ({self.row_bytes} B, bits={self.reference.bits}); "
+                             f"got rows of {width} B")
+
+    def observe(self, rows: torch.Tensor) -> None:
+        if rows.dim() != 2:
+            raise ValueError("rows must be [n, row_bytes] u8")
+        self._check(rows.shape[1])
+        with self._lock:
+            s = torch.cuda.current_stream(self.device)
+            drift_histogram(rows, self.reference.stamp, self.counts, self.tail, self.max_workgroups, s)
+            self._streams[s.cuda_stream] = s
+
+    def observe_host(self, rows: np.ndarray) -> None:
+        rows = np.asarray(rows)
+        if rows.dtype != np.uint8 or rows.ndim != 2:
+            raise ValueError("rows must be a host uint8 [k, row_bytes] array")
+        self._check(rows.shape[1])
+        with self._lock, torch.cuda.device(self.device):     # torch's current device is per thread
+            for lo in range(0, rows.shape[0], DRIFT_STAGE_ROWS):
+                chunk = rows[lo:lo + DRIFT_STAGE_ROWS]
+                b = self._next
+                self._next ^= 1
+                if self._busy[b] is not None:
+                    self._busy[b].synchronize()          # the launch that read this buffer last
+                k = chunk.shape[0]
+                self._stage[b].array[:k] = chunk
+                _drift_launch(self._stage_ptr[b], k, self.fmt, self.reference.stamp, self.counts, self.tail,
+                              self.max_workgroups, self._stream)
+                ev = torch.cuda.Event()
+                ev.record(self._stream)
+                self._busy[b] = ev
+
+    def report(self, reset: bool = False):
+        """``DriftReport`` of the window so far; ``reset=True`` starts the next one."""
+        from ..models.drift import DriftReport
+        with self._lock:
+            self._stream.synchronize()
+            for s in self._streams.values():
+                s.synchronize()
+            self._streams.clear()
+            with torch.cuda.device(self.device):
+                counts = self.counts.view(torch.int64).cpu().numpy().view(np.uint64)
+                tail = self.tail.view(torch.int64).cpu().numpy().view(np.uint64)
+                if reset:
+                    self.counts.view(torch.int64).zero_()
+                    self.tail.view(torch.int64).zero_()
+                    torch.cuda.current_stream(self.device).synchronize()
+        return DriftReport.compare(self.reference, counts, tail, self.bands, self.min_rows)
+
+    def close(self) -> None:
+        with self._lock:
+            self._stream.synchronize()
+            for p in self._stage:
+                p.free()
+            self._stage = []

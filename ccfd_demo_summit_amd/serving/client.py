@@ -26,6 +26,7 @@ class SeldonClient:
         head, _, last = endpoint.rstrip("/").rpartition("/")
         self.explain_url = _url(url, (head + "/" if head else "") + "explain") \
             if last in ("predictions", "predict") else _url(url, "explain")
+        self.drift_url = self.explain_url[:-len("explain")] + "drift"
         self.token = token
         self.timeout_s = timeout_ms / 1000.0
         self.pool_size = pool_size
@@ -65,6 +66,26 @@ class SeldonClient:
             self._aio = aiohttp.ClientSession(connector=aiohttp.TCPConnector(limit=self.pool_size),
                                               timeout=aiohttp.ClientTimeout(total=self.timeout_s))
         async with self._aio.post(self.explain_url, data=json.dumps(body), headers=self._headers()) as r:
+            r.raise_for_status()
+            return await r.json()
+
+    def drift_sync(self, reset: bool = False) -> dict:
+        """The server's drift report (``GET .../drift``); ``reset=True`` posts ``{"reset": true}``."""
+        if reset:
+            r = self._session.post(self.drift_url, data=json.dumps({"reset": True}), headers=self._headers(),
+                                   timeout=self.timeout_s)
+        else:
+            r = self._session.get(self.drift_url, headers=self._headers(), timeout=self.timeout_s)
+        r.raise_for_status()
+        return r.json()
+
+    async def drift(self, reset: bool = False) -> dict:
+        if self._aio is None or self._aio.closed:
+            self._aio = aiohttp.ClientSession(connector=aiohttp.TCPConnector(limit=self.pool_size),
+                                              timeout=aiohttp.ClientTimeout(total=self.timeout_s))
+        req = self._aio.post(self.drift_url, data=json.dumps({"reset": True}), headers=self._headers()) if reset \
+            else self._aio.get(self.drift_url, headers=self._headers())
+        async with req as r:
             r.raise_for_status()
             return await r.json()
 

@@ -7,6 +7,9 @@
 Both return ``(proba_1 float32[n], route uint8[n])`` with route = proba >= threshold.
 ``explain(X)`` (oblivious GBDT with cover only; anything else raises ``ValueError``) returns
 ``(phi float32/64 [n,30], base_value)``, the exact Shapley attributions of docs/EXPLAIN.md.
+``set_drift(reference)`` (oblivious GBDT only, likewise) makes every later ``score(X)`` batch also
+count its rows, binned against the model's table, into a drift window; ``drift()`` reports it
+(docs/DRIFT.md).
 """
 from __future__ import annotations
 
@@ -22,10 +25,44 @@ class CpuScorer:
     def __init__(self, model, threshold: float = 0.5):
         self.model = model
         self.threshold = float(threshold)
+        self._drift = None           # (reference, bins, counts, tail) after set_drift
+        self._drift_min_rows = 10_000
+        self._drift_lock = threading.Lock()
 
     def score(self, X: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
-        p = self.model.predict_proba(np.asarray(X, np.float32)).astype(np.float32)
+        X = np.asarray(X, np.float32)
+        p = self.model.predict_proba(X).astype(np.float32)
+        if self._drift is not None:
+            from ..models.drift import bin_counts
+            with self._drift_lock:
+                ref, bins, counts, tail = self._drift
+                c, t = bin_counts(bins.encode(X.reshape(-1, X.shape[-1])), ref.stamp)
+                counts += c
+                tail += t
         return p, (p >= self.threshold).astype(np.uint8)
+
+    def set_drift(self, reference, min_rows: int = 10_000) -> None:
+        """Count every later ``score`` batch against ``reference`` (``None`` turns it off)."""
+        with self._drift_lock:
+            if reference is None:
+                self._drift = None
+                return
+            bins = _drift_bins(self.model, reference)
+            self._drift_min_rows = int(min_rows)
+            self._drift = (reference, bins, np.zeros((31, 256), np.uint64), np.zeros(2, np.uint64))
+
+    def drift(self, reset: bool = False):
+        """``models.drift.DriftReport`` of the rows scored since ``set_drift`` / the last reset."""
+        from ..models.drift import DriftReport
+        with self._drift_lock:
+            if self._drift is None:
+                raise ValueError("no drift reference set (set_drift)")
+            ref, _, counts, tail = self._drift
+            rep = DriftReport.compare(ref, counts.copy(), tail.copy(), min_rows=self._drift_min_rows)
+            if reset:
+                counts[:] = 0
+                tail[:] = 0
+        return rep
 
     def explain(self, X: np.ndarray) -> Tuple[np.ndarray, float]:
         _explainable(self.model)
@@ -37,6 +74,19 @@ def _explainable(model) -> None:
     if getattr(model, "kind", None) != "gbdt":
         raise ValueError(f"model kind {getattr(model, 'kind', None)!r} has no explanation "
                          "(exact Shapley values exist for the oblivious GBDT only)")
+
+
+def _drift_bins(model, reference):
+    """The model's own bin table at the reference's width, refused unless the reference was
+    counted against it."""
+    if getattr(model, "kind", None) != "gbdt":
+        raise ValueError(f"model kind {getattr(model, 'kind', None)!r} has no drift detector "
+                         "(bin counts exist for the oblivious GBDT's split table only)")
+    bins = model.bin_spec(bits=reference.bits)
+    if not reference.compatible(bins):
+        raise ValueError(f"drift reference (stamp {reference.stamp}, {reference.bits}-bit) was not counted against "
+                         f"this model's bin table (stamp {bins.stamp})")
+    return bins
 
 
 class GpuScorer:
@@ -51,6 +101,7 @@ class GpuScorer:
         self.model = model
         self._device_index = device_index
         self._explainer = None
+        self._drift = None           # (DriftMonitor, bins) after set_drift
         self.dm = DeviceModel(model, torch.device("cuda", device_index))
         self.engine = StreamEngine(self.dm, batch=max_batch, depth=depth, streams=1,
                                    input_mode="dma", output_mode="zerocopy", threshold=threshold,
@@ -59,7 +110,33 @@ class GpuScorer:
 
     def score(self, X: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         with self._lock:
+            if self._drift is not None:
+                import torch
+                mon, bins = self._drift
+                X = np.asarray(X, np.float32)
+                rows = np.ascontiguousarray(bins.encode(X.reshape(-1, X.shape[-1])))
+                mon.observe(torch.from_numpy(rows).to(mon.device))
             return self.engine.score(X)
+
+    def set_drift(self, reference, min_rows: int = 10_000) -> None:
+        """Count every later ``score`` batch against ``reference`` with
+        csrc/kernels/drift_hist.hip (``None`` turns it off)."""
+        with self._lock:
+            if self._drift is not None:
+                self._drift[0].close()
+                self._drift = None
+            if reference is None:
+                return
+            import torch
+            from ..ops.kernels import DriftMonitor
+            bins = _drift_bins(self.model, reference)
+            self._drift = (DriftMonitor(reference, torch.device("cuda", self._device_index), min_rows=min_rows), bins)
+
+    def drift(self, reset: bool = False):
+        with self._lock:
+            if self._drift is None:
+                raise ValueError("no drift reference set (set_drift)")
+            return self._drift[0].report(reset=reset)
 
     def explain(self, X: np.ndarray) -> Tuple[np.ndarray, float]:
         """csrc/kernels/explain_gbdt.hip on the rows binned against the model's own table."""
@@ -72,6 +149,7 @@ class GpuScorer:
             return self._explainer.explain(X)
 
     def close(self):
+        self.set_drift(None)
         self.engine.close()
 
 

@@ -9,6 +9,10 @@ Endpoints (port 8000 like ``SELDON_URL=http://modelfull-modelfull:8000``, router
   POST /api/v0.1/explain, /api/v1.0/explain, /explain
                                per-feature Shapley values of the same request body (oblivious
                                GBDT with cover; docs/EXPLAIN.md); 400 for any other model
+  GET  /api/v0.1/drift, /api/v1.0/drift, /drift
+                               PSI per feature of the rows predicted so far against the drift
+                               reference (docs/DRIFT.md); POST {"reset": true} starts the next
+                               window; 400 without a reference
   GET  /prometheus, /metrics   model gauges + seldon_api_engine_* histograms
   GET  /health/ping, /health/status, /ready, /live
 
@@ -115,6 +119,9 @@ class SeldonServer:
             r.add_post(path, self.predict)
         for path in ("/api/v0.1/explain", "/api/v1.0/explain", "/explain"):
             r.add_post(path, self.explain)
+        for path in ("/api/v0.1/drift", "/api/v1.0/drift", "/drift"):
+            r.add_get(path, self.drift)
+            r.add_post(path, self.drift)
         r.add_get("/prometheus", self.prometheus)
         r.add_get("/metrics", self.prometheus)
         for path in ("/health/ping", "/ping", "/live", "/ready", "/health/status"):
@@ -189,6 +196,23 @@ class SeldonServer:
         except (seldon.SeldonError, json.JSONDecodeError, ValueError, KeyError) as e:
             return web.json_response(seldon.error_response(400, str(e)), status=400)
         return web.json_response(seldon.build_explain_response(phi, base_value, proba, self.model_name))
+
+    async def drift(self, request: web.Request) -> web.Response:
+        """The drift report of the rows predicted since the window began (``scorer.set_drift``;
+        docs/DRIFT.md) as JSON: ``names``, ``psi``, ``status``, ``rows``, ``stale``, ``worst``.
+        ``POST`` with ``{"reset": true}`` also starts the next window."""
+        if not self._authorized(request):
+            return web.json_response(seldon.error_response(401, "unauthorized"), status=401)
+        try:
+            body = await self._body(request) if request.method == "POST" else {}
+            fn = getattr(self.scorer, "drift", None)
+            if fn is None:
+                raise seldon.SeldonError("this model has no drift detector")
+            reset = bool(body.get("reset", False)) if isinstance(body, dict) else False
+            rep = await asyncio.get_running_loop().run_in_executor(None, fn, reset)
+        except (seldon.SeldonError, json.JSONDecodeError, ValueError, KeyError) as e:
+            return web.json_response(seldon.error_response(400, str(e)), status=400)
+        return web.json_response(rep.to_json())
 
     async def prometheus(self, _request: web.Request) -> web.Response:
         return web.Response(body=self.metrics.expose(), headers={"Content-Type": CONTENT_TYPE})

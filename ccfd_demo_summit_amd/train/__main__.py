@@ -69,6 +69,12 @@ def main(argv=None) -> int:
                     help="GBDT: take the split candidates from this GBDT's bin table (its bin_spec()), so the "
                          "trained ensemble packs against the table the live G32 / G20 logs were encoded with "
                          "(a challenger for `launch engine --shadow-model`); replaces --max-borders")
+    ap.add_argument("--drift-reference-out", default=None, metavar="REF.safetensors",
+                    help="GBDT: also write the drift reference of the training rows against the trained model's "
+                         "bin table (models/drift.py; `launch seldon|engine --drift-reference`)")
+    ap.add_argument("--bits", type=int, default=None, choices=[5, 8],
+                    help="--drift-reference-out: bin width of the rows the reference is for (5 = G20, 8 = G32); "
+                         "default 5 when the table fits G20 rows, else 8")
     ap.add_argument("--metrics-port", type=int, default=0,
                     help="serve the trainer's /metrics (the SparkMetrics dashboard series) on this port "
                          "(+ rank) while training; 0 = off")
@@ -128,6 +134,8 @@ def main(argv=None) -> int:
         dev = f"cuda:{torch.cuda.current_device()}"
     if a.bin_spec_from and a.model != "gbdt":
         raise SystemExit("--bin-spec-from is for --model gbdt")
+    if a.drift_reference_out and a.model != "gbdt":
+        raise SystemExit("--drift-reference-out is for --model gbdt")
     if a.model == "gbdt":
         spec = None
         if a.bin_spec_from:
@@ -144,8 +152,14 @@ def main(argv=None) -> int:
     if rank == 0:
         metrics = evaluate(model, X[te], y[te]) if n_test and 0 < y[te].sum() < n_test else {}
         save_model(model, a.out, version=a.version)
-        print(json.dumps({"model": a.model, "out": a.out, "world": world, "train": info, "holdout": metrics},
-                         default=float), flush=True)
+        out = {"model": a.model, "out": a.out, "world": world, "train": info, "holdout": metrics}
+        if a.drift_reference_out:
+            from ..models.drift import DriftReference
+            bits = a.bits or (5 if model.bin_spec().fits_g20 else 8)
+            ref = DriftReference.fit(X[tr], model.bin_spec(bits=bits))
+            ref.save(a.drift_reference_out)
+            out["drift_reference"] = {"out": a.drift_reference_out, "bits": bits, "stamp": ref.stamp, "rows": ref.rows}
+        print(json.dumps(out, default=float), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

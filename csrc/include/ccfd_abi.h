@@ -233,6 +233,30 @@ typedef struct ccfd_gbdt_explain_args {
 int ccfd_gbdt_explain_launch(const ccfd_gbdt_explain_args* a, void* stream);
 
 // ---------------------------------------------------------------------------
+// Per-feature bin counts of G32 / G20 rows, for drift detection (drift_hist.hip; models/drift.py
+// holds the definition, the numpy oracle and PSI).  For every row whose stamp equals `stamp`:
+// counts[j][bin_j] += 1 for j < 30, counts[30][amount bucket] += 1 and tail[0] += 1; a row with
+// another stamp adds 1 to tail[1] and nothing else.  G20 rows only touch cells 0..31 of a
+// column; `counts` keeps the one [31][256] shape for both formats.  The launch ACCUMULATES (it
+// never zeroes): a window is whatever the caller summed since it last zeroed the outputs.
+// Integer sums, so results are exact and bit-reproducible.  n >= 0; n == 0 returns without a
+// launch.  stamp 1..255 (G20: 1..63), max_workgroups >= 1.  A plain grid launch on `stream` of
+// min(max_workgroups, ceil(n / 1024)) workgroups.
+#define CCFD_DRIFT_COLS 31
+#define CCFD_DRIFT_CELLS 256
+typedef struct ccfd_drift_hist_args {
+  const uint8_t* rows;          // device-visible [n][32] (16-byte aligned) or [n][20] (4-byte aligned)
+  unsigned long long* counts;   // device [31][256], accumulated
+  unsigned long long* tail;     // device [2] = {rows counted, stale rows}, accumulated
+  int64_t n;
+  int32_t wire;                 // CCFD_ARG_WIRE_G32, or CCFD_ARG_WIRE_G32 | CCFD_ARG_WIRE_G20
+  int32_t stamp;                // the stamp rows must carry
+  int32_t max_workgroups;       // upper bound on the grid
+  int32_t pad;
+} ccfd_drift_hist_args;   // 48 bytes
+int ccfd_drift_hist_launch(const ccfd_drift_hist_args* a, void* stream);
+
+// ---------------------------------------------------------------------------
 // Persistent streaming kernel (exec_mode = 1): ONE long-running launch per engine; the
 // host publishes micro-batch descriptors into a ring in coherent pinned memory and bumps
 // `posted`; resident workgroups claim 64..256-row work items with one device atomic, wait for

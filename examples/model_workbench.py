@@ -107,6 +107,13 @@ def main(argv=None) -> dict:
         print(f"row {int(i)}: log-odds {base_value + row.sum():+.3f} = base {base_value:+.3f} "
               + " ".join(f"{w['feature']} {w['phi']:+.3f}" for w in why) + " ...")
 
+    # %% does the holdout still look like the training rows?  (PSI per feature, docs/DRIFT.md)
+    from ccfd_demo_summit_amd.models.drift import DriftReference, DriftReport, bin_counts
+    ref = DriftReference.fit(Xtr, spec)
+    drift = DriftReport.compare(ref, *bin_counts(rows, spec.stamp))
+    report["drift"] = {"rows": drift.rows, "worst": [{"feature": n, "psi": v, "status": s} for n, v, s in drift.worst(3)]}
+    print("drift train -> holdout, worst PSI: " + ", ".join(f"{n} {v:.4f} ({s})" for n, v, s in drift.worst(3)))
+
     # %% score through the MI355X kernels
     if torch.cuda.is_available() and device.startswith("cuda"):
         from ccfd_demo_summit_amd.engine import StreamEngine
