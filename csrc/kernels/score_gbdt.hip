@@ -186,7 +186,9 @@ __global__ __launch_bounds__(256) void score_gbdt_v2_kernel(ccfd_score_args a) {
   {
     const float4* s4 = reinterpret_cast<const float4*>(leaves);
     float4* d4 = reinterpret_cast<float4*>(lv);
-    for (int i = tid; i < T * L / 4; i += 256) d4[i] = s4[i];
+    const int nl = T * L;
+    for (int i = tid; i < nl / 4; i += 256) d4[i] = s4[i];
+    for (int i = (nl & ~3) + tid; i < nl; i += 256) lv[i] = leaves[i];   // depth 1, odd T: 2 floats past the last float4
   }
 
   // one 64-row chunk = 480 float4; lane l holds float4 l + 64k (k < 8)

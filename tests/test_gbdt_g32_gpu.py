@@ -45,17 +45,25 @@ def test_g32_kernel_exact(gpu, data, n, depth):
 
 
 def test_g32_large_launch_and_r2(gpu, monkeypatch):
-    """A 1M-row HBM-resident launch (grid-stride, several chunks per wave)."""
+    """A 1M-row HBM-resident launch (grid-stride, several chunks per wave), with one 64-row
+    chunk per wave step (the default) and with two (CCFD_G32_R=2, read per launch)."""
     from ccfd_demo_summit_amd.ops.kernels import DeviceModel, new_counters, score
     X, _ = generate(1 << 20, seed=43)
     m = build_model("gbdt", seed=5, X_ref=X[:5000], calibrate_rate=0.01)
     dm = DeviceModel(m, gpu, bins=True)
-    cnt = new_counters(gpu)
-    p, r = score(dm, torch.from_numpy(dm.bins.encode(X)).to(gpu), 0.5, counters=cnt)
-    torch.cuda.synchronize(gpu)
-    p = p.cpu().numpy()
-    assert np.abs(p - m.predict_proba(X)).max() < 1e-5
-    _check_counters(cnt, p, r.cpu().numpy(), X)
+    rows = torch.from_numpy(dm.bins.encode(X)).to(gpu)
+    ref = m.predict_proba(X)
+    for chunks in (None, "2"):
+        if chunks is None:
+            monkeypatch.delenv("CCFD_G32_R", raising=False)
+        else:
+            monkeypatch.setenv("CCFD_G32_R", chunks)
+        cnt = new_counters(gpu)
+        p, r = score(dm, rows, 0.5, counters=cnt)
+        torch.cuda.synchronize(gpu)
+        p = p.cpu().numpy()
+        assert np.abs(p - ref).max() < 1e-5, chunks
+        _check_counters(cnt, p, r.cpu().numpy(), X)
 
 
 def test_g32_stale_stamp_rows_counted_not_scored(gpu, data):
