@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "../include/ccfd_abi.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -16,6 +18,31 @@ constexpr int kNB = CCFD_N_AMOUNT_BUCKETS;   // 13 finite bounds + Inf
 constexpr int kTileRows = 16;                // rows per 16x16x32 MFMA tile (one wave)
 constexpr int kTileBytes = kTileRows * kF * 4;   // 1920: contiguous when ld == 30
 constexpr int kHeader = 64;
+
+// GBB1 blob of a T x D oblivious ensemble: the header (base score f32 at byte 16), then three
+// sections -- 0: feature ids, 1: thresholds (f32 rows) or bin indices (binned rows), 2: leaf
+// tables -- the first two padded to 16 bytes.
+__device__ __forceinline__ const char* gbb_section(const char* blob, int T, int D, int k) {
+  const int tdw = ((4 * T * D + 15) & ~15) / 4;          // dwords of section 0 and of section 1
+  return reinterpret_cast<const char*>(reinterpret_cast<const float*>(blob + kHeader) + k * tdw);
+}
+__device__ __forceinline__ float gbb_base(const char* blob) { return *reinterpret_cast<const float*>(blob + 16); }
+
+// Runtime tree depth -> compile-time D: f(std::integral_constant<int, D>{}).  The caller has
+// checked 1 <= depth <= 8.
+template <class F>
+inline auto dispatch_depth(int depth, F&& f) {
+  switch (depth) {
+    case 1: return f(std::integral_constant<int, 1>{});
+    case 2: return f(std::integral_constant<int, 2>{});
+    case 3: return f(std::integral_constant<int, 3>{});
+    case 4: return f(std::integral_constant<int, 4>{});
+    case 5: return f(std::integral_constant<int, 5>{});
+    case 6: return f(std::integral_constant<int, 6>{});
+    case 7: return f(std::integral_constant<int, 7>{});
+    default: return f(std::integral_constant<int, 8>{});
+  }
+}
 
 // Row loads and output stores through the GLOBAL address space.  A generic pointer (every
 // pointer read from a descriptor or struct) compiles to FLAT instructions, and a FLAT

@@ -222,16 +222,7 @@ extern "C" int ccfd_gbdt_explain_launch(const ccfd_gbdt_explain_args* a, void* s
   if (chunk >= kExplainWaves) chunk -= chunk % kExplainWaves;
   chunk = std::min(chunk, (int)a->trees);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  switch (a->depth) {
-    case 1: launch_explain<1>(*a, chunk, s); break;
-    case 2: launch_explain<2>(*a, chunk, s); break;
-    case 3: launch_explain<3>(*a, chunk, s); break;
-    case 4: launch_explain<4>(*a, chunk, s); break;
-    case 5: launch_explain<5>(*a, chunk, s); break;
-    case 6: launch_explain<6>(*a, chunk, s); break;
-    case 7: launch_explain<7>(*a, chunk, s); break;
-    default: launch_explain<8>(*a, chunk, s); break;
-  }
+  dispatch_depth(a->depth, [&](auto d) { launch_explain<decltype(d)::value>(*a, chunk, s); });
   if (const hipError_t e = hipGetLastError(); e != hipSuccess) {
     set_error(std::string("gbdt explain: launch failed: ") + hipGetErrorString(e));
     return -5;

@@ -1,6 +1,10 @@
-// Shared device code of the G32 oblivious-GBDT kernels (score_gbdt_g32.hip: one launch per
-// micro-batch; score_gbdt_g32_persist.hip: the persistent variant).  Two translation units
-// so the many (depth x rules x leaf-placement) instantiations compile in parallel.
+// Shared device code of the binned-row (G32 / G20) oblivious-GBDT kernels: score_gbdt_g32.hip
+// (one launch per micro-batch), score_gbdt_g32_persist.hip (persistent: claimed and pipelined
+// items) and score_gbdt_shadow.hip (a challenger beside the champion, launch and persistent).
+// Separate translation units so the many (depth x rules x leaf-placement) instantiations
+// compile in parallel.  Here: the row formats (fetch, transpose, lift), the tree walk, the
+// view of a GBB1 blob (G32Model), and what every kernel does with a scored row (g32_row_epilogue,
+// g32_wave_commit / g32_item_commit).
 //
 // Oblivious-GBDT scorer over G32 rows (BASELINE.json configs[3]: 100 trees x depth 6,
 // batch 65536) -- the exact low-byte wire for tree ensembles.
@@ -198,12 +202,28 @@ __device__ __forceinline__ unsigned gx_lift(const G32Row& r, unsigned (&b)[kF]) 
   else return g32_lift(r, b);
 }
 
-// Stage the T * 2^D leaf table (blob section after feat / kbin) into LDS.
+// One GBB1 blob of T trees x depth D as the binned-row kernels read it.  Split parameters
+// through the CONSTANT address space: wave-uniform indices compile to s_load into SGPRs (the
+// blob is immutable for the kernel's lifetime).
+struct G32Model {
+  g32_cint_p feat, kbin;
+  const float* leaves;   // T * 2^D floats in the blob (global memory)
+  float base;
+  unsigned stamp;        // of the bin table the rows must carry
+};
+
 template <int D>
-__device__ __forceinline__ void g32_stage_leaves(const char* blob, int T, float* lv, int tid, int nthreads) {
+__device__ __forceinline__ G32Model g32_model(const void* blob_, int T) {
+  const char* blob = reinterpret_cast<const char*>(blob_);
+  return G32Model{(g32_cint_p)gbb_section(blob, T, D, 0), (g32_cint_p)gbb_section(blob, T, D, 1),
+                  reinterpret_cast<const float*>(gbb_section(blob, T, D, 2)), gbb_base(blob),
+                  (unsigned)*reinterpret_cast<const int*>(blob + 20)};
+}
+
+// Stage a T * 2^D leaf table into LDS.
+template <int D>
+__device__ __forceinline__ void g32_stage_leaves(const float* src, int T, float* lv, int tid, int nthreads) {
   constexpr int L = 1 << D;
-  const int tdw = ((4 * T * D + 15) & ~15) / 4;
-  const float* src = reinterpret_cast<const float*>(blob + kHeader + 8 * tdw);
   const float4* s4 = reinterpret_cast<const float4*>(src);
   float4* d4 = reinterpret_cast<float4*>(lv);
   const int nl = T * L;
@@ -211,12 +231,99 @@ __device__ __forceinline__ void g32_stage_leaves(const char* blob, int T, float*
   for (int i = (nl & ~3) + tid; i < nl; i += nthreads) lv[i] = src[i];
 }
 
-// Leaf tables of T * 2^D floats up to kG32LeafLds are staged in LDS; larger ensembles
-// (kGL: e.g. CatBoost's default 1000 x depth 6 = 250 KB) gather their leaves straight from
-// the blob in global memory -- read-only and L2-resident, one gather per tree and row chain.
-__device__ __forceinline__ const float* g32_leaves_global(const char* blob, int T, int D) {
-  const int tdw = ((4 * T * D + 15) & ~15) / 4;
-  return reinterpret_cast<const float*>(blob + kHeader + 8 * tdw);
+// The leaf table the tree walk reads.  Tables of T * 2^D floats up to kG32LeafLds are staged
+// into `lv` (LDS; the caller's barrier follows); larger ensembles (kGL: e.g. CatBoost's
+// default 1000 x depth 6 = 250 KB) gather their leaves straight from the blob in global
+// memory -- read-only and L2-resident, one gather per tree and row chain.
+template <int D, bool kGL>
+__device__ __forceinline__ const float* g32_leaves(const G32Model& M, int T, float* lv, int tid, int nthreads) {
+  if constexpr (kGL) return M.leaves;
+  g32_stage_leaves<D>(M.leaves, T, lv, tid, nthreads);
+  return lv;
+}
+
+// Per-wave counts of the rows scored so far (a launch: all of them; a persistent kernel: the
+// wave's share of one item).
+struct G32Wave {
+  unsigned fraud = 0, rows = 0, stale = 0;
+  unsigned long long psum = 0;
+};
+
+struct G32RowOut {
+  bool valid, fresh, fr;         // inside the batch; carries the model's bin stamp; routed to fraud
+  float p;                       // NaN for a stale row
+  unsigned long long m;          // __ballot(fr)
+};
+
+// What every binned-row kernel does with a lane's scored row: sigmoid of the leaf sum `acc`
+// (stale rows -- meta = bucket | stamp << 8 of another bin table -- are counted, not scored),
+// route by threshold or proba-only rules (kR), proba / route outputs, the workgroup's amount
+// histogram and the wave's counts.  The flag list stays with the caller (emit_flagged and
+// persist_emit_flagged are different protocols).
+template <bool kR>
+__device__ __forceinline__ G32RowOut g32_row_epilogue(EpilogueLds& epi, G32Wave& w, const G32Model& M, unsigned meta,
+                                                      float acc, int row, int n, float threshold,
+                                                      const ccfd_rule_prog* rules, float* proba, uint8_t* route) {
+  const bool valid = row < n;
+  const bool fresh = ((meta >> 8) & 0xffu) == M.stamp;
+  const float p = fresh ? sigmoid(M.base + acc) : __builtin_nanf("");
+  bool fr;
+  if constexpr (kR) fr = valid && fresh && rule_route(rules, p, [](int) { return 0.f; });
+  else fr = valid && fresh && (p >= threshold);
+  if (valid) {
+#ifndef CCFD_EXP_NO_OUTPUTS   // experiment build only: cost of the output stream, dropped by EVERY binned-row kernel
+    if (proba) st_g(proba + row, p);
+    if (route) st_g(route + row, (uint8_t)(fr ? 1 : 0));
+#endif
+    if (fresh) w.psum += (unsigned)(p * 1e6f + 0.5f);
+    atomicAdd(&epi.hist[(fr ? kNB : 0) + min((int)(meta & 0xffu), kNB - 1)], 1u);
+  }
+  const unsigned long long m = __ballot(fr);
+  w.fraud += __popcll(m);
+  w.rows += __popcll(__ballot(valid));
+  w.stale += __popcll(__ballot(valid && !fresh));
+  return G32RowOut{valid, fresh, fr, p, m};
+}
+
+// Wave -> workgroup (LDS) at the end of a launch; stale rows straight into `cnt`.
+__device__ __forceinline__ void g32_wave_commit(EpilogueLds& epi, G32Wave& w, unsigned long long* cnt, int lane) {
+  w.psum = wave_sum_u64(w.psum);
+  if (lane == 0) {
+    atomicAdd(&epi.fraud, w.fraud);
+    atomicAdd(&epi.rows, w.rows);
+    atomicAdd(&epi.psum_e6, w.psum);
+  }
+  if (cnt != nullptr && lane == 0 && w.stale) atomicAdd(&cnt[CCFD_CNT_WIRE_STALE], (unsigned long long)w.stale);
+}
+
+// The same at the end of a persistent item (`cnt`: the item's epoch buffer): a wave that had
+// no rows of the item adds nothing, and the counts start over for the next item.
+__device__ __forceinline__ void g32_item_commit(EpilogueLds& epi, G32Wave& w, unsigned long long* cnt, int lane) {
+  w.psum = wave_sum_u64(w.psum);
+  if (lane == 0 && w.rows) {
+    atomicAdd(&epi.fraud, w.fraud);
+    atomicAdd(&epi.rows, w.rows);
+    atomicAdd(&epi.psum_e6, w.psum);
+    if (w.stale && cnt) atomicAdd(&cnt[CCFD_CNT_WIRE_STALE], (unsigned long long)w.stale);
+  }
+  w = G32Wave{};
+}
+
+// A persistent kernel's work item `it` (C items a micro-batch, `chunks` 64-row chunks an item
+// over kW waves) as wave `wave` sees it: the wave scores chunks c0, c0 + kW, ...
+struct G32Item {
+  int slot, n, c0;
+  const unsigned char* xb;
+};
+
+// `stamp`: this thread stamps the micro-batch's start (K7) if the item is its first.
+__device__ __forceinline__ G32Item g32_item(const ccfd_persist_args& a, const ccfd_persist_desc& d, unsigned long long it,
+                                            int C, int chunks, int wave, bool stamp) {
+  const int item = (int)(it % (unsigned long long)C);
+  const int slot = (int)(d.seq % (unsigned long long)a.ring);
+  if (item == 0 && stamp)
+    __hip_atomic_store(&a.dev->tstart[slot], wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return G32Item{slot, d.n, item * chunks + wave, reinterpret_cast<const unsigned char*>(d.x)};
 }
 
 // read per launch, so in-process sweeps can vary it

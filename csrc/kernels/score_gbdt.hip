@@ -48,11 +48,10 @@ __global__ __launch_bounds__(256) void score_gbdt_kernel(ccfd_score_args a, int 
 
   const char* blob = reinterpret_cast<const char*>(a.blob);
   const int T = a.gbdt_trees;
-  const float base = *reinterpret_cast<const float*>(blob + 16);
-  const int* __restrict__ feat = reinterpret_cast<const int*>(blob + kHeader);
-  const int tdw = ((4 * T * D + 15) & ~15) / 4;
-  const float* __restrict__ thr = reinterpret_cast<const float*>(blob + kHeader) + tdw;
-  const float* __restrict__ leaves = thr + tdw;
+  const float base = gbb_base(blob);
+  const int* __restrict__ feat = reinterpret_cast<const int*>(gbb_section(blob, T, D, 0));
+  const float* __restrict__ thr = reinterpret_cast<const float*>(gbb_section(blob, T, D, 1));
+  const float* __restrict__ leaves = reinterpret_cast<const float*>(gbb_section(blob, T, D, 2));
   const int kChunk = min(T, kLeafLds / L);
   const bool resident = kChunk == T;
 
@@ -174,15 +173,14 @@ __global__ __launch_bounds__(256) void score_gbdt_v2_kernel(ccfd_score_args a) {
 
   const char* blob = reinterpret_cast<const char*>(a.blob);
   const int T = a.gbdt_trees;
-  const float base = *reinterpret_cast<const float*>(blob + 16);
-  const int tdw = ((4 * T * D + 15) & ~15) / 4;
+  const float base = gbb_base(blob);
   // split parameters through the CONSTANT address space: wave-uniform indices then compile
   // to s_load into SGPRs (the model blob is immutable for the kernel's lifetime)
   typedef const __attribute__((address_space(4))) int* cint_p;
   typedef const __attribute__((address_space(4))) float* cflt_p;
-  const cint_p feat = (cint_p)(blob + kHeader);
-  const cflt_p thr = (cflt_p)(blob + kHeader + 4 * tdw);
-  const float* __restrict__ leaves = reinterpret_cast<const float*>(blob + kHeader) + 2 * tdw;
+  const cint_p feat = (cint_p)gbb_section(blob, T, D, 0);
+  const cflt_p thr = (cflt_p)gbb_section(blob, T, D, 1);
+  const float* __restrict__ leaves = reinterpret_cast<const float*>(gbb_section(blob, T, D, 2));
   {
     const float4* s4 = reinterpret_cast<const float4*>(leaves);
     float4* d4 = reinterpret_cast<float4*>(lv);
@@ -397,29 +395,11 @@ int launch_gbdt(const ccfd_score_args& a, hipStream_t s) {
   const bool want_v2 = forced == 2 || (forced == 0 && a.n >= kGbV2MinRows);
   if (want_v2 && contig && a.gbdt_depth >= 1 && a.gbdt_depth <= 8 &&
       ((long)a.gbdt_trees << a.gbdt_depth) <= kLeafLds) {
-    switch (a.gbdt_depth) {
-      case 1: launch_d2<1>(a, s); break;
-      case 2: launch_d2<2>(a, s); break;
-      case 3: launch_d2<3>(a, s); break;
-      case 4: launch_d2<4>(a, s); break;
-      case 5: launch_d2<5>(a, s); break;
-      case 6: launch_d2<6>(a, s); break;
-      case 7: launch_d2<7>(a, s); break;
-      default: launch_d2<8>(a, s); break;
-    }
+    dispatch_depth(a.gbdt_depth, [&](auto d) { launch_d2<decltype(d)::value>(a, s); });
     return hipGetLastError() == hipSuccess ? 0 : -5;
   }
-  switch (a.gbdt_depth) {
-    case 1: launch_d<1>(a, s, contig); break;
-    case 2: launch_d<2>(a, s, contig); break;
-    case 3: launch_d<3>(a, s, contig); break;
-    case 4: launch_d<4>(a, s, contig); break;
-    case 5: launch_d<5>(a, s, contig); break;
-    case 6: launch_d<6>(a, s, contig); break;
-    case 7: launch_d<7>(a, s, contig); break;
-    case 8: launch_d<8>(a, s, contig); break;
-    default: return -2;
-  }
+  if (a.gbdt_depth < 1 || a.gbdt_depth > 8) return -2;
+  dispatch_depth(a.gbdt_depth, [&](auto d) { launch_d<decltype(d)::value>(a, s, contig); });
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

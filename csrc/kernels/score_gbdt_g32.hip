@@ -27,22 +27,12 @@ __global__ __launch_bounds__(256) void score_gbdt_g32_kernel(ccfd_score_args a) 
 
   epi_init(epi);
   stamp_start(a, blockIdx.x);
-  const char* blob = reinterpret_cast<const char*>(a.blob);
   const int T = a.gbdt_trees;
-  const float base = *reinterpret_cast<const float*>(blob + 16);
-  const unsigned stamp = (unsigned)*reinterpret_cast<const int*>(blob + 20);
-  const int tdw = ((4 * T * D + 15) & ~15) / 4;
-  // split parameters through the CONSTANT address space: wave-uniform indices compile to
-  // s_load into SGPRs (the model blob is immutable for the kernel's lifetime)
-  const g32_cint_p feat = (g32_cint_p)(blob + kHeader);
-  const g32_cint_p kbin = (g32_cint_p)(blob + kHeader + 4 * tdw);
-  const float* leaves = lv;
-  if constexpr (kGL) leaves = g32_leaves_global(blob, T, D);
-  else g32_stage_leaves<D>(blob, T, lv, tid, 256);
+  const G32Model M = g32_model<D>(a.blob, T);
+  const float* leaves = g32_leaves<D, kGL>(M, T, lv, tid, 256);
   __syncthreads();                                              // leaves staged, epi initialised
 
-  unsigned fraud = 0, rows = 0, stale = 0;
-  unsigned long long psum = 0;
+  G32Wave w;
   for (; grp < ngroups; grp += gstride) {
     // separate 1-D arrays per row chain: indexed by a runtime (wave-uniform) feature id they
     // stay in VGPRs (v_movrel); a 2-D array would be demoted to scratch
@@ -62,37 +52,16 @@ __global__ __launch_bounds__(256) void score_gbdt_g32_kernel(ccfd_score_args a) 
       for (int q = 0; q < R; ++q) gx_fetch<kG20>(xb, n, nxt * R + q, lane, pre[q]);
     }
     float acc[R];
-    g32_trees<D, R>(b0, b1, leaves, feat, kbin, T, acc);
+    g32_trees<D, R>(b0, b1, leaves, M.feat, M.kbin, T, acc);
 #pragma unroll
     for (int q = 0; q < R; ++q) {
       const int row = (grp * R + q) * kG32Rows + lane;
-      const bool valid = row < n;
-      const bool fresh = ((meta[q] >> 8) & 0xffu) == stamp;
-      const float p = fresh ? sigmoid(base + acc[q]) : __builtin_nanf("");
-      bool fr;
-      if constexpr (kR) fr = valid && fresh && rule_route(a.rules, p, [](int) { return 0.f; });
-      else fr = valid && fresh && (p >= a.threshold);
-      if (valid) {
-        if (a.proba) st_g(a.proba + row, p);
-        if (a.route) st_g(a.route + row, (uint8_t)(fr ? 1 : 0));
-        if (fresh) psum += (unsigned)(p * 1e6f + 0.5f);
-        atomicAdd(&epi.hist[(fr ? kNB : 0) + min((int)(meta[q] & 0xffu), kNB - 1)], 1u);
-      }
-      fraud += __popcll(__ballot(fr));
-      rows += __popcll(__ballot(valid));
-      stale += __popcll(__ballot(valid && !fresh));
-      emit_flagged(a, fr, row);
+      const G32RowOut o = g32_row_epilogue<kR>(epi, w, M, meta[q], acc[q], row, n, a.threshold, a.rules, a.proba, a.route);
+      emit_flagged(a, o.fr, row);
     }
   }
-  psum = wave_sum_u64(psum);
-  if (lane == 0) {
-    atomicAdd(&epi.fraud, fraud);
-    atomicAdd(&epi.rows, rows);
-    atomicAdd(&epi.psum_e6, psum);
-  }
-  unsigned long long* cnt = a.counters;
-  if (cnt != nullptr && lane == 0 && stale) atomicAdd(&cnt[CCFD_CNT_WIRE_STALE], (unsigned long long)stale);
-  epi_flush(epi, cnt);
+  g32_wave_commit(epi, w, a.counters, lane);
+  epi_flush(epi, a.counters);
   signal_done(a, gridDim.x);
 }
 
@@ -136,16 +105,7 @@ static void launch_g32_d(const ccfd_score_args& a, hipStream_t s) {
 int launch_gbdt_g32(const ccfd_score_args& a, hipStream_t s) {
   if (a.gbdt_trees <= 0 || a.gbdt_depth < 1 || a.gbdt_depth > 8) return -2;
   if (a.n <= 0) return 0;
-  switch (a.gbdt_depth) {
-    case 1: launch_g32_d<1>(a, s); break;
-    case 2: launch_g32_d<2>(a, s); break;
-    case 3: launch_g32_d<3>(a, s); break;
-    case 4: launch_g32_d<4>(a, s); break;
-    case 5: launch_g32_d<5>(a, s); break;
-    case 6: launch_g32_d<6>(a, s); break;
-    case 7: launch_g32_d<7>(a, s); break;
-    default: launch_g32_d<8>(a, s); break;
-  }
+  dispatch_depth(a.gbdt_depth, [&](auto d) { launch_g32_d<decltype(d)::value>(a, s); });
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

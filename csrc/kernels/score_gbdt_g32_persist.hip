@@ -56,48 +56,16 @@ __global__ __launch_bounds__(64 * kW) void persist_gbdt_g32_kernel(ccfd_persist_
     if (wave == 0) persist_doorbell(a, lane);
     return;                                               // no barrier is ever used by WG 0
   }
-  const char* blob = reinterpret_cast<const char*>(a.blob);
   const int T = a.gbdt_trees;
-  const float base = *reinterpret_cast<const float*>(blob + 16);
-  const unsigned stamp = (unsigned)*reinterpret_cast<const int*>(blob + 20);
-  const int tdw = ((4 * T * D + 15) & ~15) / 4;
-  const g32_cint_p feat = (g32_cint_p)(blob + kHeader);
-  const g32_cint_p kbin = (g32_cint_p)(blob + kHeader + 4 * tdw);
-  const float* leaves = lv;
-  if constexpr (kGL) leaves = g32_leaves_global(blob, T, D);
-  else g32_stage_leaves<D>(blob, T, lv, tid, 64 * kW);
+  const G32Model M = g32_model<D>(a.blob, T);
+  const float* leaves = g32_leaves<D, kGL>(M, T, lv, tid, 64 * kW);
   epi_init(epi);
   __syncthreads();
   unsigned long long posted_cache = 0;                    // thread 0 only
 
-  // per-item accumulators of this wave (flushed by item_flush)
-  unsigned fraud = 0, rows = 0, stale = 0;
-  unsigned long long psum = 0;
-  // sigmoid, route, outputs, histogram and flag list of one scored 64-row chunk
-  auto chunk_epilogue = [&](const ccfd_persist_desc& d, int slot, int n, int chunk, unsigned meta, float acc)
-      __attribute__((always_inline)) {
-    const int row = chunk * kG32Rows + lane;
-    const bool valid = row < n;
-    const bool fresh = ((meta >> 8) & 0xffu) == stamp;
-    const float p = fresh ? sigmoid(base + acc) : __builtin_nanf("");
-    bool fr;
-    if constexpr (kR) fr = valid && fresh && rule_route(a.rules, p, [](int) { return 0.f; });
-    else fr = valid && fresh && (p >= a.threshold);
-    if (valid) {
-#ifndef CCFD_EXP_NO_OUTPUTS                                // experiment build only: cost of the output stream
-      if (d.proba) st_g(d.proba + row, p);
-      if (d.route) st_g(d.route + row, (uint8_t)(fr ? 1 : 0));
-#endif
-      if (fresh) psum += (unsigned)(p * 1e6f + 0.5f);
-      atomicAdd(&epi.hist[(fr ? kNB : 0) + min((int)(meta & 0xffu), kNB - 1)], 1u);
-    }
-    const unsigned long long m = __ballot(fr);
-    fraud += __popcll(m);
-    rows += __popcll(__ballot(valid));
-    stale += __popcll(__ballot(valid && !fresh));
-    persist_emit_flagged(a, d, slot, m, fr, row, lane);
-  };
-  auto score_chunk = [&](const ccfd_persist_desc& d, int slot, int n, int chunk, G32Row& cur)
+  G32Wave w;                                              // this wave's share of the item (g32_item_commit)
+  // transpose, lift, trees, row epilogue and flag list of one fetched 64-row chunk
+  auto score_chunk = [&](const ccfd_persist_desc& d, const G32Item& it, int chunk, G32Row& cur)
       __attribute__((always_inline)) {
     gx_rows<kG20>(xt[wave], lane, cur);
     unsigned b0[kF];
@@ -108,26 +76,11 @@ __global__ __launch_bounds__(64 * kW) void persist_gbdt_g32_kernel(ccfd_persist_
     // by a use of the bins -- what the persistent read + completion path alone sustains
     acc[0] = (float)(b0[0] + b0[kF - 1]) * 1e-3f;
 #else
-    g32_trees<D, 1>(b0, b0, leaves, feat, kbin, T, acc);
+    g32_trees<D, 1>(b0, b0, leaves, M.feat, M.kbin, T, acc);
 #endif
-    chunk_epilogue(d, slot, n, chunk, meta, acc[0]);
-  };
-  auto item_flush = [&](const ccfd_persist_desc& d, int slot) __attribute__((always_inline)) {
-    psum = wave_sum_u64(psum);
-    if (lane == 0 && rows) {
-      atomicAdd(&epi.fraud, fraud);
-      atomicAdd(&epi.rows, rows);
-      atomicAdd(&epi.psum_e6, psum);
-      unsigned long long* cnt = a.counters[d.epoch & 1];
-      if (stale && cnt) atomicAdd(&cnt[CCFD_CNT_WIRE_STALE], (unsigned long long)stale);
-    }
-    fraud = rows = stale = 0;
-    psum = 0;
-    persist_item_done(a, epi, d, slot, C, tid);
-  };
-  auto k7_start = [&](unsigned long long it, int slot) __attribute__((always_inline)) {
-    if (it % (unsigned long long)C == 0 && tid == 0)      // K7: micro-batch start (item 0 claimed first)
-      __hip_atomic_store(&a.dev->tstart[slot], wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int row = chunk * kG32Rows + lane;
+    const G32RowOut o = g32_row_epilogue<kR>(epi, w, M, meta, acc[0], row, it.n, a.threshold, a.rules, d.proba, d.route);
+    persist_emit_flagged(a, d, it.slot, o.m, o.fr, row, lane);
   };
 
   for (;;) {
@@ -161,12 +114,9 @@ __global__ __launch_bounds__(64 * kW) void persist_gbdt_g32_kernel(ccfd_persist_
     __syncthreads();
     if (s_cmd) break;
     const ccfd_persist_desc d = sdesc;                     // registers: no LDS wait in the epilogue
-    const int item = (int)(s_item % (unsigned long long)C);
-    const int slot = (int)(d.seq % (unsigned long long)a.ring);
-    const int n = d.n;
-    const unsigned char* xb = reinterpret_cast<const unsigned char*>(d.x);
-    k7_start(s_item, slot);
-    const int c0 = item * (kW * cpw) + wave;              // this wave's chunks: c0 + kW*k
+    const G32Item it = g32_item(a, d, s_item, C, kW * cpw, wave, tid == 0);   // K7: item 0 is claimed first
+    const int n = it.n, c0 = it.c0;                       // this wave's chunks: c0 + kW*k
+    const unsigned char* xb = it.xb;
     // CCFD_G32_INFLIGHT=1: every chunk of the wave's share of the item in flight at once
     // (static registers: no copy of a pending load, so no vmcnt(0) between chunks)
     auto full_item = [&](auto kC) __attribute__((always_inline)) {
@@ -181,7 +131,7 @@ __global__ __launch_bounds__(64 * kW) void persist_gbdt_g32_kernel(ccfd_persist_
       for (int k = 0; k < CPW; ++k) {
         const int chunk = c0 + kW * k;
         if (chunk * kG32Rows >= n) break;                 // wave-uniform
-        score_chunk(d, slot, n, chunk, r[k]);
+        score_chunk(d, it, chunk, r[k]);
       }
     };
     if (a.flags & CCFD_ARG_CHUNK_RING) {                  // default: one chunk ahead
@@ -194,7 +144,7 @@ __global__ __launch_bounds__(64 * kW) void persist_gbdt_g32_kernel(ccfd_persist_
         G32Row cur_row = pre;
         CCFD_ITRACE(if (k == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); if (tid == 0) t_load = wall_clock64(); })
         if (k + 1 < cpw && (chunk + kW) * kG32Rows < n) gx_fetch<kG20>(xb, n, chunk + kW, lane, pre);
-        score_chunk(d, slot, n, chunk, cur_row);
+        score_chunk(d, it, chunk, cur_row);
       }
     } else if (cpw == 1) {
       full_item(std::integral_constant<int, 1>{});
@@ -204,7 +154,8 @@ __global__ __launch_bounds__(64 * kW) void persist_gbdt_g32_kernel(ccfd_persist_
       full_item(std::integral_constant<int, 4>{});        // 1024-row items (engine accepts 256/512/1024)
     }
     CCFD_ITRACE(if (tid == 0) t_scored = wall_clock64();)
-    item_flush(d, slot);
+    g32_item_commit(epi, w, a.counters[d.epoch & 1], lane);
+    persist_item_done(a, epi, d, it.slot, C, tid);
 #ifdef CCFD_EXP_ITEM_TRACE
     if (tid == 0) {
       const unsigned long long k =
@@ -246,15 +197,9 @@ __global__ __launch_bounds__(256) void persist_gbdt_pipe_kernel(ccfd_persist_arg
     if (wave == 0) persist_doorbell(a, lane);
     return;
   }
-  const char* blob = reinterpret_cast<const char*>(a.blob);
   const int T = a.gbdt_trees;
-  const float base = *reinterpret_cast<const float*>(blob + 16);
-  const unsigned stamp = (unsigned)*reinterpret_cast<const int*>(blob + 20);
-  const int tdw = ((4 * T * D + 15) & ~15) / 4;
-  const g32_cint_p feat = (g32_cint_p)(blob + kHeader);
-  const g32_cint_p kbin = (g32_cint_p)(blob + kHeader + 4 * tdw);
-  g32_stage_leaves<D>(blob, T, lv, tid, 256);
-  const float* leaves = lv;
+  const G32Model M = g32_model<D>(a.blob, T);
+  const float* leaves = g32_leaves<D, false>(M, T, lv, tid, 256);
   epi_init(epi);
   __syncthreads();
   const unsigned long long W = gridDim.x - 1;
@@ -262,65 +207,36 @@ __global__ __launch_bounds__(256) void persist_gbdt_pipe_kernel(ccfd_persist_arg
                             (unsigned long long)(blockIdx.x - 1);
   unsigned long long posted_cache = 0;                    // thread 0 only
 
-  unsigned fraud = 0, rows = 0, stale = 0;
-  unsigned long long psum = 0;
+  G32Wave w;
+  // thread 0, as soon as it has read an item's descriptor: K7 stamp if the item starts a micro-batch
   auto k7 = [&](const ccfd_persist_desc& d, unsigned long long it) __attribute__((always_inline)) {
-    if (it % (unsigned long long)C == 0)                  // K7: micro-batch start
-      __hip_atomic_store(&a.dev->tstart[d.seq % (unsigned long long)a.ring], wall_clock64(), __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
+    g32_item(a, d, it, C, kG32Waves * CPW, wave, true);
   };
   auto issue = [&](const ccfd_persist_desc& d, unsigned long long it, G32Row (&r)[CPW]) __attribute__((always_inline)) {
-    const int c0 = (int)(it % (unsigned long long)C) * (kG32Waves * CPW) + wave;
-    const unsigned char* xb = reinterpret_cast<const unsigned char*>(d.x);
+    const G32Item i = g32_item(a, d, it, C, kG32Waves * CPW, wave, false);
 #pragma unroll
     for (int k = 0; k < CPW; ++k) {
-      const int chunk = c0 + kG32Waves * k;
-      if (chunk * kG32Rows < d.n) gx_fetch<kG20>(xb, d.n, chunk, lane, r[k]);
+      const int chunk = i.c0 + kG32Waves * k;
+      if (chunk * kG32Rows < i.n) gx_fetch<kG20>(i.xb, i.n, chunk, lane, r[k]);
     }
   };
   auto score = [&](const ccfd_persist_desc& d, unsigned long long it, G32Row (&r)[CPW]) __attribute__((always_inline)) {
-    const int slot = (int)(d.seq % (unsigned long long)a.ring);
-    const int n = d.n;
-    const int c0 = (int)(it % (unsigned long long)C) * (kG32Waves * CPW) + wave;
+    const G32Item i = g32_item(a, d, it, C, kG32Waves * CPW, wave, false);
 #pragma unroll
     for (int k = 0; k < CPW; ++k) {
-      const int chunk = c0 + kG32Waves * k;
-      if (chunk * kG32Rows >= n) break;                   // wave-uniform
+      const int chunk = i.c0 + kG32Waves * k;
+      if (chunk * kG32Rows >= i.n) break;                 // wave-uniform
       gx_rows<kG20>(xt[wave], lane, r[k]);
       unsigned b0[kF];
       const unsigned meta = gx_lift<kG20>(r[k], b0);
       float acc[1];
-      g32_trees<D, 1>(b0, b0, leaves, feat, kbin, T, acc);
+      g32_trees<D, 1>(b0, b0, leaves, M.feat, M.kbin, T, acc);
       const int row = chunk * kG32Rows + lane;
-      const bool valid = row < n;
-      const bool fresh = ((meta >> 8) & 0xffu) == stamp;
-      const float p = fresh ? sigmoid(base + acc[0]) : __builtin_nanf("");
-      bool fr;
-      if constexpr (kR) fr = valid && fresh && rule_route(a.rules, p, [](int) { return 0.f; });
-      else fr = valid && fresh && (p >= a.threshold);
-      if (valid) {
-        if (d.proba) st_g(d.proba + row, p);
-        if (d.route) st_g(d.route + row, (uint8_t)(fr ? 1 : 0));
-        if (fresh) psum += (unsigned)(p * 1e6f + 0.5f);
-        atomicAdd(&epi.hist[(fr ? kNB : 0) + min((int)(meta & 0xffu), kNB - 1)], 1u);
-      }
-      const unsigned long long m = __ballot(fr);
-      fraud += __popcll(m);
-      rows += __popcll(__ballot(valid));
-      stale += __popcll(__ballot(valid && !fresh));
-      persist_emit_flagged(a, d, slot, m, fr, row, lane);
+      const G32RowOut o = g32_row_epilogue<kR>(epi, w, M, meta, acc[0], row, i.n, a.threshold, a.rules, d.proba, d.route);
+      persist_emit_flagged(a, d, i.slot, o.m, o.fr, row, lane);
     }
-    psum = wave_sum_u64(psum);
-    if (lane == 0 && rows) {
-      atomicAdd(&epi.fraud, fraud);
-      atomicAdd(&epi.rows, rows);
-      atomicAdd(&epi.psum_e6, psum);
-      unsigned long long* cnt = a.counters[d.epoch & 1];
-      if (stale && cnt) atomicAdd(&cnt[CCFD_CNT_WIRE_STALE], (unsigned long long)stale);
-    }
-    fraud = rows = stale = 0;
-    psum = 0;
-    persist_item_done(a, epi, d, slot, C, tid);           // barriers, release, ticket
+    g32_item_commit(epi, w, a.counters[d.epoch & 1], lane);
+    persist_item_done(a, epi, d, i.slot, C, tid);         // barriers, release, ticket
   };
   // score `it` from (dc, rc) while item it + W is fetched into (dn, rn); true = host stopped
   auto stage = [&](ccfd_persist_desc& dc, G32Row (&rc)[CPW], ccfd_persist_desc& dn, G32Row (&rn)[CPW],
@@ -397,12 +313,6 @@ static int launch_persist_g32_f(const ccfd_persist_args& a0, int grid, hipStream
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
-template <int D>
-static int launch_persist_g32_d(const ccfd_persist_args& a, int grid, hipStream_t s) {
-  return (a.flags & CCFD_ARG_WIRE_G20) ? launch_persist_g32_f<D, true>(a, grid, s)
-                                       : launch_persist_g32_f<D, false>(a, grid, s);
-}
-
 #ifdef CCFD_EXP_ITEM_TRACE
 // host: the item ring -> <path> as {u64 n, ItemTrace[kItemTraceCap]} (record k at k % cap), then the
 // doorbell ring (persist_core.h)
@@ -430,16 +340,10 @@ int item_trace_dump(const char* path) {
 
 int launch_persist_gbdt_g32(const ccfd_persist_args& a, int grid, hipStream_t s) {
   if (a.gbdt_trees <= 0 || a.gbdt_depth < 1 || a.gbdt_depth > 8) return -2;
-  switch (a.gbdt_depth) {
-    case 1: return launch_persist_g32_d<1>(a, grid, s);
-    case 2: return launch_persist_g32_d<2>(a, grid, s);
-    case 3: return launch_persist_g32_d<3>(a, grid, s);
-    case 4: return launch_persist_g32_d<4>(a, grid, s);
-    case 5: return launch_persist_g32_d<5>(a, grid, s);
-    case 6: return launch_persist_g32_d<6>(a, grid, s);
-    case 7: return launch_persist_g32_d<7>(a, grid, s);
-    default: return launch_persist_g32_d<8>(a, grid, s);
-  }
+  return dispatch_depth(a.gbdt_depth, [&](auto d) {
+    return (a.flags & CCFD_ARG_WIRE_G20) ? launch_persist_g32_f<decltype(d)::value, true>(a, grid, s)
+                                         : launch_persist_g32_f<decltype(d)::value, false>(a, grid, s);
+  });
 }
 
 }  // namespace ccfd

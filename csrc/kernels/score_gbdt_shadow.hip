@@ -13,10 +13,11 @@
 //     one-chunk prefetch ring; doorbell workgroup, claim, item completion and flag list are
 //     those of persist_core.h, unchanged.
 //
-// The champion's epilogue is what the champion kernels do (proba, route, flag list, amount
-// histogram, counters, completion record).  The challenger adds the five CCFD_CNT_SHADOW_*
-// counters (shadow_core.h) and, in the launch kernel, its proba_1 per row when asked to.
-// Stale rows (bin stamp != the champion blob's) are counted in no shadow slot.
+// The champion's epilogue is what the champion kernels do (g32_core.h g32_row_epilogue: proba,
+// route, amount histogram, counters; then flag list and completion record).  The challenger
+// adds the five CCFD_CNT_SHADOW_* counters (shadow_core.h) and, in the launch kernel, its
+// proba_1 per row when asked to.  Stale rows (bin stamp != the champion blob's) are counted in
+// no shadow slot.
 //
 // The challenger has the champion's shape (T trees x depth D) and bin table: the host side
 // checks that, the kernels trust it.  Leaf tables: the champion's placement follows its own
@@ -31,27 +32,61 @@ namespace ccfd {
 
 namespace {
 
-// Split parameters and leaf table of one GBB1 blob.
-struct G32Model {
-  g32_cint_p feat, kbin;
-  float base;
-};
-
-template <int D>
-__device__ __forceinline__ G32Model g32_model(const char* blob, int T) {
-  const int tdw = ((4 * T * D + 15) & ~15) / 4;
-  // CONSTANT address space: wave-uniform indices compile to scalar loads (g32_core.h)
-  return G32Model{(g32_cint_p)(blob + kHeader), (g32_cint_p)(blob + kHeader + 4 * tdw),
-                  *reinterpret_cast<const float*>(blob + 16)};
-}
-
 // LDS offset (floats) of the challenger's leaf table behind the champion's: 16-byte aligned
 // for the float4 staging copy (T * 2^D is odd or 2 mod 4 only at depth 1).
 __host__ __device__ constexpr int shadow_leaf_off(int T, int D) { return ((T << D) + 3) & ~3; }
 
+// Champion A and challenger B of a kernel, leaf tables placed (kGL / kGS: the champion's /
+// the challenger's leaves from global memory; kGL implies kGS); the caller's barrier follows.
+struct ShadowPair {
+  G32Model A, B;
+  const float *leavesA, *leavesB;
+  int T;
+};
+
+template <int D, bool kGL, bool kGS>
+__device__ __forceinline__ ShadowPair shadow_pair(const void* blobA, const void* blobB, int T, float* lv, int tid) {
+  ShadowPair m{g32_model<D>(blobA, T), g32_model<D>(blobB, T), nullptr, nullptr, T};
+  m.leavesA = g32_leaves<D, kGL>(m.A, T, lv, tid, 256);
+  m.leavesB = g32_leaves<D, kGS>(m.B, T, lv + shadow_leaf_off(T, D), tid, 256);
+  return m;
+}
+
+// This wave's counts: the champion's, the challenger's, and the fresh rows both scored.
+struct ShadowWave {
+  G32Wave w;
+  ShadowAcc sw;
+  unsigned srows = 0;
+};
+
+// One fetched 64-row chunk through both ensembles: transpose, lift, two tree walks, the
+// champion's row epilogue and the challenger's bookkeeping.  Returns the champion's row for
+// the caller's flag list.  `b0`: the 30 registers the bins are lifted into, declared in the
+// caller's loop body (declared here, the persistent kernel needs 6 more VGPRs and loses a wave
+// per SIMD at depths 4..6).
+template <int D, bool kG20>
+__device__ __forceinline__ G32RowOut shadow_chunk(const ShadowPair& m, uint4* xt, G32Row& cur, unsigned (&b0)[kF],
+                                                  int lane, int row, int n, float thr, EpilogueLds& epi, ShadowWave& s,
+                                                  float* proba, uint8_t* route, float* shadow_proba) {
+  gx_rows<kG20>(xt, lane, cur);
+  const unsigned meta = gx_lift<kG20>(cur, b0);                // bucket | stamp << 8
+  float accA[1], accB[1];
+  g32_trees<D, 1>(b0, b0, m.leavesA, m.A.feat, m.A.kbin, m.T, accA);
+  g32_trees<D, 1>(b0, b0, m.leavesB, m.B.feat, m.B.kbin, m.T, accB);
+  const G32RowOut o = g32_row_epilogue<false>(epi, s.w, m.A, meta, accA[0], row, n, thr, nullptr, proba, route);
+  const bool scored = o.valid && o.fresh;
+  const float q = o.fresh ? sigmoid(m.B.base + accB[0]) : __builtin_nanf("");
+  const bool sf = scored && (q >= thr);
+  if (o.valid && shadow_proba) st_g(shadow_proba + row, q);
+  if (scored) shadow_row(s.sw, o.p, q);
+  s.srows += __popcll(__ballot(scored));
+  s.sw.fraud += __popcll(__ballot(sf));
+  s.sw.both += __popcll(__ballot(sf && o.fr));
+  return o;
+}
+
 // ---------------------------------------------------------------------------------------
-// Launch kernel.  kGL: champion leaves from global memory; kGS: challenger leaves from
-// global memory (kGL implies kGS).
+// Launch kernel.
 // ---------------------------------------------------------------------------------------
 template <int D, bool kGL, bool kGS, bool kG20>
 __global__ __launch_bounds__(256) void score_gbdt_shadow_kernel(ccfd_shadow_args sa) {
@@ -77,69 +112,25 @@ __global__ __launch_bounds__(256) void score_gbdt_shadow_kernel(ccfd_shadow_args
   epi_init(epi);
   shadow_init(sh);
   stamp_start(a, blockIdx.x);
-  const char* blobA = reinterpret_cast<const char*>(a.blob);
-  const char* blobB = reinterpret_cast<const char*>(sa.shadow_blob);
-  const int T = a.gbdt_trees;
-  const unsigned stamp = (unsigned)*reinterpret_cast<const int*>(blobA + 20);
-  const G32Model A = g32_model<D>(blobA, T), B = g32_model<D>(blobB, T);
-  const float* leavesA = lv;
-  const float* leavesB = lv + shadow_leaf_off(T, D);
-  if constexpr (kGL) leavesA = g32_leaves_global(blobA, T, D);
-  else g32_stage_leaves<D>(blobA, T, lv, tid, 256);
-  if constexpr (kGS) leavesB = g32_leaves_global(blobB, T, D);
-  else g32_stage_leaves<D>(blobB, T, lv + shadow_leaf_off(T, D), tid, 256);
+  const ShadowPair m = shadow_pair<D, kGL, kGS>(a.blob, sa.shadow_blob, a.gbdt_trees, lv, tid);
   __syncthreads();                                              // leaves staged, epi / sh initialised
 
   const float thr = a.threshold;
-  unsigned fraud = 0, rows = 0, stale = 0, srows = 0;
-  unsigned long long psum = 0;
-  ShadowAcc sw;
+  ShadowWave s;
   for (; chunk < nchunks; chunk += gstride) {
-    unsigned b0[kF];
     G32Row cur = pre;
-    gx_rows<kG20>(xt[wave], lane, cur);
-    const unsigned meta = gx_lift<kG20>(cur, b0);              // bucket | stamp << 8
     const int nxt = chunk + gstride;
     if (nxt < nchunks) gx_fetch<kG20>(xb, n, nxt, lane, pre);
-    float accA[1], accB[1];
-    g32_trees<D, 1>(b0, b0, leavesA, A.feat, A.kbin, T, accA);
-    g32_trees<D, 1>(b0, b0, leavesB, B.feat, B.kbin, T, accB);
+    unsigned b0[kF];
     const int row = chunk * kG32Rows + lane;
-    const bool valid = row < n;
-    const bool fresh = ((meta >> 8) & 0xffu) == stamp;
-    const float p = fresh ? sigmoid(A.base + accA[0]) : __builtin_nanf("");
-    const float q = fresh ? sigmoid(B.base + accB[0]) : __builtin_nanf("");
-    const bool fr = valid && fresh && (p >= thr);
-    const bool sf = valid && fresh && (q >= thr);
-    if (valid) {
-      if (a.proba) st_g(a.proba + row, p);
-      if (a.route) st_g(a.route + row, (uint8_t)(fr ? 1 : 0));
-      if (sa.shadow_proba) st_g(sa.shadow_proba + row, q);
-      if (fresh) {
-        psum += (unsigned)(p * 1e6f + 0.5f);
-        shadow_row(sw, p, q);
-      }
-      atomicAdd(&epi.hist[(fr ? kNB : 0) + min((int)(meta & 0xffu), kNB - 1)], 1u);
-    }
-    fraud += __popcll(__ballot(fr));
-    rows += __popcll(__ballot(valid));
-    stale += __popcll(__ballot(valid && !fresh));
-    srows += __popcll(__ballot(valid && fresh));
-    sw.fraud += __popcll(__ballot(sf));
-    sw.both += __popcll(__ballot(sf && fr));
-    emit_flagged(a, fr, row);
+    const G32RowOut o = shadow_chunk<D, kG20>(m, xt[wave], cur, b0, lane, row, n, thr, epi, s, a.proba, a.route,
+                                              sa.shadow_proba);
+    emit_flagged(a, o.fr, row);
   }
-  psum = wave_sum_u64(psum);
-  if (lane == 0) {
-    atomicAdd(&epi.fraud, fraud);
-    atomicAdd(&epi.rows, rows);
-    atomicAdd(&epi.psum_e6, psum);
-  }
-  shadow_wave_commit(sh, sw, srows, lane);
-  unsigned long long* cnt = a.counters;
-  if (cnt != nullptr && lane == 0 && stale) atomicAdd(&cnt[CCFD_CNT_WIRE_STALE], (unsigned long long)stale);
-  epi_flush(epi, cnt);                                          // barrier first, then the champion's atomics
-  if (tid == 2 * kNB + 1) shadow_flush(sh, cnt);
+  g32_wave_commit(epi, s.w, a.counters, lane);
+  shadow_wave_commit(sh, s.sw, s.srows, lane);
+  epi_flush(epi, a.counters);                                   // barrier first, then the champion's atomics
+  if (tid == 2 * kNB + 1) shadow_flush(sh, a.counters);
   signal_done(a, gridDim.x);
 }
 
@@ -167,17 +158,7 @@ __global__ __launch_bounds__(256) void persist_gbdt_shadow_kernel(ccfd_persist_s
     if (wave == 0) persist_doorbell(a, lane);
     return;                                               // no barrier is ever used by WG 0
   }
-  const char* blobA = reinterpret_cast<const char*>(a.blob);
-  const char* blobB = reinterpret_cast<const char*>(sa.shadow_blob);
-  const int T = a.gbdt_trees;
-  const unsigned stamp = (unsigned)*reinterpret_cast<const int*>(blobA + 20);
-  const G32Model A = g32_model<D>(blobA, T), B = g32_model<D>(blobB, T);
-  const float* leavesA = lv;
-  const float* leavesB = lv + shadow_leaf_off(T, D);
-  if constexpr (kGL) leavesA = g32_leaves_global(blobA, T, D);
-  else g32_stage_leaves<D>(blobA, T, lv, tid, 256);
-  if constexpr (kGS) leavesB = g32_leaves_global(blobB, T, D);
-  else g32_stage_leaves<D>(blobB, T, lv + shadow_leaf_off(T, D), tid, 256);
+  const ShadowPair m = shadow_pair<D, kGL, kGS>(a.blob, sa.shadow_blob, a.gbdt_trees, lv, tid);
   epi_init(epi);
   shadow_init(sh);
   __syncthreads();
@@ -189,65 +170,27 @@ __global__ __launch_bounds__(256) void persist_gbdt_shadow_kernel(ccfd_persist_s
     __syncthreads();
     if (s_cmd) break;
     const ccfd_persist_desc d = sdesc;                     // registers: no LDS wait in the epilogue
-    const int item = (int)(s_item % (unsigned long long)C);
-    const int slot = (int)(d.seq % (unsigned long long)a.ring);
-    const int n = d.n;
-    const unsigned char* xb = reinterpret_cast<const unsigned char*>(d.x);
-    if (item == 0 && tid == 0)                             // K7: micro-batch start (item 0 claimed first)
-      __hip_atomic_store(&a.dev->tstart[slot], wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int c0 = item * (kG32Waves * cpw) + wave;        // this wave's chunks: c0 + 4k
+    const G32Item it = g32_item(a, d, s_item, C, kG32Waves * cpw, wave, tid == 0);   // K7: item 0 is claimed first
+    const int n = it.n;
 
-    unsigned fraud = 0, rows = 0, stale = 0, srows = 0;    // this wave's share of the item
-    unsigned long long psum = 0;
-    ShadowAcc sw;
+    ShadowWave s;                                          // this wave's share of the item
     G32Row pre;
-    if (c0 * kG32Rows < n) gx_fetch<kG20>(xb, n, c0, lane, pre);
+    if (it.c0 * kG32Rows < n) gx_fetch<kG20>(it.xb, n, it.c0, lane, pre);
 #pragma unroll 1
     for (int k = 0; k < cpw; ++k) {
-      const int chunk = c0 + kG32Waves * k;
+      const int chunk = it.c0 + kG32Waves * k;             // this wave's chunks: c0 + 4k
       if (chunk * kG32Rows >= n) break;                    // wave-uniform
       G32Row cur = pre;
-      if (k + 1 < cpw && (chunk + kG32Waves) * kG32Rows < n) gx_fetch<kG20>(xb, n, chunk + kG32Waves, lane, pre);
-      gx_rows<kG20>(xt[wave], lane, cur);
+      if (k + 1 < cpw && (chunk + kG32Waves) * kG32Rows < n) gx_fetch<kG20>(it.xb, n, chunk + kG32Waves, lane, pre);
       unsigned b0[kF];
-      const unsigned meta = gx_lift<kG20>(cur, b0);
-      float accA[1], accB[1];
-      g32_trees<D, 1>(b0, b0, leavesA, A.feat, A.kbin, T, accA);
-      g32_trees<D, 1>(b0, b0, leavesB, B.feat, B.kbin, T, accB);
       const int row = chunk * kG32Rows + lane;
-      const bool valid = row < n;
-      const bool fresh = ((meta >> 8) & 0xffu) == stamp;
-      const float p = fresh ? sigmoid(A.base + accA[0]) : __builtin_nanf("");
-      const float q = fresh ? sigmoid(B.base + accB[0]) : __builtin_nanf("");
-      const bool fr = valid && fresh && (p >= thr);
-      const bool sf = valid && fresh && (q >= thr);
-      if (valid) {
-        if (d.proba) st_g(d.proba + row, p);
-        if (d.route) st_g(d.route + row, (uint8_t)(fr ? 1 : 0));
-        if (fresh) {
-          psum += (unsigned)(p * 1e6f + 0.5f);
-          shadow_row(sw, p, q);
-        }
-        atomicAdd(&epi.hist[(fr ? kNB : 0) + min((int)(meta & 0xffu), kNB - 1)], 1u);
-      }
-      const unsigned long long m = __ballot(fr);
-      fraud += __popcll(m);
-      rows += __popcll(__ballot(valid));
-      stale += __popcll(__ballot(valid && !fresh));
-      srows += __popcll(__ballot(valid && fresh));
-      sw.fraud += __popcll(__ballot(sf));
-      sw.both += __popcll(__ballot(sf && fr));
-      persist_emit_flagged(a, d, slot, m, fr, row, lane);
+      const G32RowOut o = shadow_chunk<D, kG20>(m, xt[wave], cur, b0, lane, row, n, thr, epi, s, d.proba, d.route,
+                                                nullptr);
+      persist_emit_flagged(a, d, it.slot, o.m, o.fr, row, lane);
     }
-    psum = wave_sum_u64(psum);
     unsigned long long* cnt = a.counters[d.epoch & 1];
-    if (lane == 0 && rows) {
-      atomicAdd(&epi.fraud, fraud);
-      atomicAdd(&epi.rows, rows);
-      atomicAdd(&epi.psum_e6, psum);
-      if (stale && cnt) atomicAdd(&cnt[CCFD_CNT_WIRE_STALE], (unsigned long long)stale);
-    }
-    shadow_wave_commit(sh, sw, srows, lane);
+    g32_item_commit(epi, s.w, cnt, lane);
+    shadow_wave_commit(sh, s.sw, s.srows, lane);
     // the item's challenger counters, then LDS reset for the next item: persist_item_done's
     // barriers and its vmcnt(0) drain order both before the item's ticket and the next claim
     __syncthreads();
@@ -255,7 +198,7 @@ __global__ __launch_bounds__(256) void persist_gbdt_shadow_kernel(ccfd_persist_s
       shadow_flush(sh, cnt);
       sh.rows = 0; sh.fraud = 0; sh.both = 0; sh.psum_e6 = 0; sh.absdiff_e6 = 0;
     }
-    persist_item_done(a, epi, d, slot, C, tid);
+    persist_item_done(a, epi, d, it.slot, C, tid);
   }
 }
 
@@ -292,12 +235,6 @@ void launch_shadow_f(const ccfd_shadow_args& sa, hipStream_t s) {
   else hipLaunchKernelGGL((score_gbdt_shadow_kernel<D, false, false, kG20>), dim3(grid), dim3(256), p.lds, s, sa);
 }
 
-template <int D>
-void launch_shadow_d(const ccfd_shadow_args& sa, hipStream_t s) {
-  if (sa.base.flags & CCFD_ARG_WIRE_G20) launch_shadow_f<D, true>(sa, s);
-  else launch_shadow_f<D, false>(sa, s);
-}
-
 template <int D, bool kG20>
 int launch_persist_shadow_f(const ccfd_persist_shadow_args& sa, int grid, hipStream_t s) {
   const ShadowLeafPlan p = shadow_leaf_plan(sa.base.gbdt_trees, D, kG32LeafLds);
@@ -307,44 +244,26 @@ int launch_persist_shadow_f(const ccfd_persist_shadow_args& sa, int grid, hipStr
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
-template <int D>
-int launch_persist_shadow_d(const ccfd_persist_shadow_args& sa, int grid, hipStream_t s) {
-  return (sa.base.flags & CCFD_ARG_WIRE_G20) ? launch_persist_shadow_f<D, true>(sa, grid, s)
-                                             : launch_persist_shadow_f<D, false>(sa, grid, s);
-}
-
 }  // namespace
 
 int launch_gbdt_shadow(const ccfd_shadow_args& sa, hipStream_t s) {
   const ccfd_score_args& a = sa.base;
   if (a.gbdt_trees <= 0 || a.gbdt_depth < 1 || a.gbdt_depth > 8) return -2;
   if (a.n <= 0) return 0;
-  switch (a.gbdt_depth) {
-    case 1: launch_shadow_d<1>(sa, s); break;
-    case 2: launch_shadow_d<2>(sa, s); break;
-    case 3: launch_shadow_d<3>(sa, s); break;
-    case 4: launch_shadow_d<4>(sa, s); break;
-    case 5: launch_shadow_d<5>(sa, s); break;
-    case 6: launch_shadow_d<6>(sa, s); break;
-    case 7: launch_shadow_d<7>(sa, s); break;
-    default: launch_shadow_d<8>(sa, s); break;
-  }
+  dispatch_depth(a.gbdt_depth, [&](auto d) {
+    if (a.flags & CCFD_ARG_WIRE_G20) launch_shadow_f<decltype(d)::value, true>(sa, s);
+    else launch_shadow_f<decltype(d)::value, false>(sa, s);
+  });
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
 int launch_persist_gbdt_shadow(const ccfd_persist_shadow_args& sa, int grid, hipStream_t s) {
   const ccfd_persist_args& a = sa.base;
   if (a.gbdt_trees <= 0 || a.gbdt_depth < 1 || a.gbdt_depth > 8) return -2;
-  switch (a.gbdt_depth) {
-    case 1: return launch_persist_shadow_d<1>(sa, grid, s);
-    case 2: return launch_persist_shadow_d<2>(sa, grid, s);
-    case 3: return launch_persist_shadow_d<3>(sa, grid, s);
-    case 4: return launch_persist_shadow_d<4>(sa, grid, s);
-    case 5: return launch_persist_shadow_d<5>(sa, grid, s);
-    case 6: return launch_persist_shadow_d<6>(sa, grid, s);
-    case 7: return launch_persist_shadow_d<7>(sa, grid, s);
-    default: return launch_persist_shadow_d<8>(sa, grid, s);
-  }
+  return dispatch_depth(a.gbdt_depth, [&](auto d) {
+    return (a.flags & CCFD_ARG_WIRE_G20) ? launch_persist_shadow_f<decltype(d)::value, true>(sa, grid, s)
+                                         : launch_persist_shadow_f<decltype(d)::value, false>(sa, grid, s);
+  });
 }
 
 }  // namespace ccfd
