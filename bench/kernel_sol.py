@@ -14,6 +14,7 @@ compared with the two ceilings of the kernel on MI355X:
     python bench/kernel_sol.py --cases mlp:w64 --sizes 16777216 --flags 48   # ablation
     python bench/kernel_sol.py --cases forest:f32,gbdt:f32 --sizes 1048576,16777216            # general trees:
     python bench/kernel_sol.py --cases forest:f32 --forest random --forest-lds-multiple 4      # LDS / L2 node table
+    python bench/kernel_sol.py --cases forest:f32,forest:g32,forest:g20 --sizes 16777216       # ... on binned rows
 """
 from __future__ import annotations
 
@@ -71,7 +72,7 @@ def main():
     ap.add_argument("--gbdt-trees", type=int, default=100)
     ap.add_argument("--gbdt-depth", type=int, default=6)
     ap.add_argument("--forest", default="oblivious", choices=["oblivious", "random"],
-                    help="forest:f32 case: the --gbdt-trees x --gbdt-depth ensemble expanded into general trees "
+                    help="forest:f32 / forest:g32 / forest:g20 cases: the --gbdt-trees x --gbdt-depth ensemble expanded into general trees "
                          "(node table in LDS when it fits), or random unbalanced depth-12 trees")
     ap.add_argument("--forest-lds-multiple", type=float, default=4.0,
                     help="--forest random: node table of about this many times the kernel's LDS budget "

@@ -321,7 +321,7 @@ class StreamEngine:
                  shadow: Optional[DeviceModel] = None):
         """exec_mode: "launch" = one fused kernel launch per micro-batch; "persistent" = one
         long-running kernel fed through a descriptor ring (MLP/LR, zero-copy outputs; general
-        trees -- kind "forest" -- have a launch-mode kernel only).
+        trees -- kind "forest", on f32, G32 or G20 rows -- have launch-mode kernels only).
         persist_items (persistent MLP on W64 rows): "claimed" = 512-row items claimed by 64
         workgroups (the throughput point: 8.7e8 tx/s at 12 batches in flight); "pipelined" =
         static 128-row items over 128 workgroups with the next item's rows fetched while the

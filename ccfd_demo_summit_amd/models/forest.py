@@ -1,6 +1,7 @@
 """General (non-oblivious) binary decision-tree ensembles: random forests, extra trees,
 scikit-learn / XGBoost boosted trees (importers: models/sklearn_import.py,
-models/xgboost_import.py; device kernel: csrc/kernels/score_forest.hip).
+models/xgboost_import.py; device kernels: csrc/kernels/score_forest.hip for f32 rows,
+csrc/kernels/score_forest_bins.hip for G32 / G20 rows).
 
 Every inner node has its own test: a row goes RIGHT iff ``x[feat] > thr`` as a float32
 compare -- the predicate of the oblivious kernels, so NaN goes left (transactions are dense
@@ -22,6 +23,12 @@ Blob for the kernel (16-B aligned sections):
             v            = threshold of an inner node, value of a leaf
           a leaf's child field is its own index, so one step of the walk is
           ``next = leaf ? cur : child + (x[feat] > v)`` and a finished row stays put.
+
+Binned rows (G32 / G20, contracts/transaction.py; device kernel: csrc/kernels/score_forest_bins.hip)
+work for any tree: with a ``BinSpec`` whose edges contain the ensemble's thresholds, ``x > edges[k]``
+<=> ``bin > k`` for every float (NaN -> bin 0 -> left).  The 'FRB1' blob is the FRS1 blob with the
+spec's stamp in the header word at byte 24 and, for an inner node, ``v`` = the bin index k of its
+threshold as u32 (255 for a NaN threshold, which never fires); leaves keep their f32 value.
 """
 from __future__ import annotations
 
@@ -33,7 +40,7 @@ import numpy as np
 
 from ..contracts.transaction import N_FEATURES
 from .common import HEADER_BYTES, header, pad16, sigmoid
-from .gbdt import ObliviousGBDT
+from .gbdt import MAX_BINS, BinSpec, ObliviousGBDT
 
 MAX_DEPTH = 64
 MAX_NODES = 1 << 24              # the blob's child field is 24 bits
@@ -218,17 +225,59 @@ class TreeEnsemble:
                    0.0, link)
 
     # ------------------------------------------------------------------ device blob
-    def pack(self, wire: bool = False, bins=None) -> bytes:
-        """FRS1 blob (f32 rows; general trees have no W64 / binned-row kernels)."""
-        if wire or bins is not None:
-            raise ValueError("general trees score f32 rows only (no W64 wire rows, no G32 / G20 bins)")
+    def _split_nodes(self) -> np.ndarray:
+        """Indices of the inner nodes a walk can reach (nodes no root leads to are never tested)."""
+        return np.flatnonzero(~self.leaf & (self.node_tree >= 0))
+
+    def bin_spec(self, bits: int = 8) -> BinSpec:
+        """The smallest bin table of this ensemble -- the distinct non-NaN thresholds of its
+        reachable inner nodes, per feature -- for G32 rows (``bits=8``; ValueError past 255
+        thresholds a feature: such a forest keeps f32 rows) or G20 rows (``bits=5``; past 31)."""
+        i = self._split_nodes()
+        spec = BinSpec.from_thresholds(self.feat[i], self.value[i])
+        return spec if bits == 8 else spec.with_bits(bits)
+
+    def leaf_node_binned(self, rows: np.ndarray, bins: Optional[BinSpec] = None) -> np.ndarray:
+        """``leaf_node`` from binned rows (u8 [n,32] G32 rows, or [n,20] G20 rows of a 5-bit
+        spec; ``BinSpec.encode``) -- the device walk's form of every step, ``bin[feat] > k`` with
+        k the threshold's edge index -- [n, T]."""
+        spec = bins if bins is not None else self.bin_spec()
+        k = np.zeros(self.n_nodes, np.int32)
+        i = self._split_nodes()
+        k[i] = spec.bin_index(self.feat[i], self.value[i])               # NaN thresholds: 255
+        if spec.bits == 5:
+            from ..contracts.transaction import decode_g20_bins
+            b = decode_g20_bins(rows).astype(np.int32)
+        else:
+            b = np.asarray(rows, np.uint8)[:, :N_FEATURES].astype(np.int32)
+        cur = np.broadcast_to(self.root[None, :], (b.shape[0], self.n_trees)).astype(np.int64)
+        r = np.arange(b.shape[0])[:, None]
+        for _ in range(self.depth):
+            right = b[r, self.feat[cur]] > k[cur]
+            cur = np.where(self.leaf[cur], cur, self.child[cur] + right)
+        return cur
+
+    def pack(self, wire: bool = False, bins: Optional[BinSpec] = None) -> bytes:
+        """FRS1 blob for f32 rows, or (``bins``) the FRB1 blob for G32 / G20 rows of that spec;
+        a threshold that is not one of its edges raises ``BinSpec``'s ValueError.  General trees
+        have no W64 kernel."""
+        if wire:
+            raise ValueError("general trees score f32 rows, or G32 / G20 rows (bins=): no W64 wire rows")
         w = (self.feat.astype(np.uint32) | (self.leaf.astype(np.uint32) << 5) | (self.child.astype(np.uint32) << 8))
         node = np.empty((self.n_nodes, 2), np.uint32)
         node[:, 0] = w
         node[:, 1] = self.value.view(np.uint32)
         tree = np.stack([self.root, self.tree_depth], 1).astype(np.int32)
-        blob = header(b"FRS1", 1 if self.link == "sigmoid" else 0, self.n_trees, self.depth, float(self.base),
-                      self.n_nodes)
+        flags = 1 if self.link == "sigmoid" else 0
+        if bins is None:
+            blob = header(b"FRS1", flags, self.n_trees, self.depth, float(self.base), self.n_nodes)
+        else:
+            inner = np.flatnonzero(~self.leaf)
+            reach = self.node_tree[inner] >= 0
+            k = np.full(inner.size, MAX_BINS, np.int32)                  # unreachable: never fires
+            k[reach] = bins.bin_index(self.feat[inner[reach]], self.value[inner[reach]])
+            node[inner, 1] = k.astype(np.uint32)
+            blob = header(b"FRB1", flags, self.n_trees, self.depth, float(self.base), self.n_nodes, int(bins.stamp))
         return blob + pad16(tree.tobytes()) + pad16(node.tobytes())
 
     @classmethod

@@ -30,17 +30,20 @@ class DeviceModel:
         ``bins``: GBDT on binned rows -- ``True`` for the model's own G32 bin table, ``"g20"``
         for the same table on 20-byte G20 rows (<= 31 thresholds a feature), or a
         ``models.gbdt.BinSpec`` containing its thresholds (e.g. the live logs' spec; its
-        ``bits`` select G32 or G20).  A ``TreeEnsemble`` (kind "forest") takes neither: the
-        general-tree kernel scores f32 rows."""
+        ``bits`` select G32 or G20).  A ``TreeEnsemble`` (kind "forest") scores f32 rows by
+        default and binned rows when asked by name: ``bins="g32"``, ``bins="g20"`` or a
+        ``BinSpec``; ``bins=True`` is refused for it."""
         self.kind = model.kind
         if self.kind not in MODEL_IDS:
             raise ValueError(f"no device kernel for model kind {self.kind!r}")
         if wire and self.kind not in ("mlp", "lr"):
             raise ValueError("W64 wire rows are supported by the MLP and LR kernels" if self.kind != "forest" else
-                             "general trees (forest) score f32 rows only: no wire=")
-        if bins is not None and bins is not False and self.kind != "gbdt":
-            raise ValueError("G32 rows (bins=) are for the GBDT kernel" if self.kind != "forest" else
-                             "general trees (forest) score f32 rows only: no bins=")
+                             "general trees (forest) score f32 rows, or G32 / G20 rows (bins=): no wire=")
+        if bins is not None and bins is not False and self.kind not in ("gbdt", "forest"):
+            raise ValueError("G32 rows (bins=) are for the GBDT and general-tree kernels")
+        if bins is True and self.kind == "forest":
+            raise ValueError("general trees (forest) score f32 rows unless a binned format is named: "
+                             "bins=\"g32\", bins=\"g20\" or bins=<BinSpec>, not bins=True")
         self.wire = bool(wire)
         if bins is True or bins == "g32":
             bins = model.bin_spec()

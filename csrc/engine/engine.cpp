@@ -258,8 +258,11 @@ class Engine {
     if (cfg.blob == nullptr) { set_error("null model blob"); return -1; }
     if (cfg.wire < 0 || cfg.wire > 3) { set_error("wire must be 0 (f32), 1 (W64), 2 (G32) or 3 (G20)"); return -1; }
     if (cfg.wire == 1 && cfg.model == CCFD_MODEL_GBDT) { set_error("W64 wire rows: MLP and LR only"); return -1; }
-    if (cfg.wire >= 2 && cfg.model != CCFD_MODEL_GBDT) { set_error("G32 / G20 rows: GBDT only"); return -1; }
-    if (cfg.wire != 0 && cfg.model == CCFD_MODEL_FOREST) { set_error("forest models score f32 rows only"); return -1; }
+    if (cfg.wire >= 2 && cfg.model != CCFD_MODEL_GBDT && cfg.model != CCFD_MODEL_FOREST) {
+      set_error("G32 / G20 rows: GBDT and forest models only");
+      return -1;
+    }
+    if (cfg.wire == 1 && cfg.model == CCFD_MODEL_FOREST) { set_error("forest models score f32, G32 or G20 rows"); return -1; }
     rowf = cfg.wire == 3 ? CCFD_G20_ROW_BYTES / 4 : cfg.wire == 2 ? CCFD_G32_ROW_BYTES / 4
          : cfg.wire ? CCFD_WIRE_ROW_BYTES / 4 : CCFD_N_FEATURES;
     amount_f = cfg.wire >= 2 ? -1 : cfg.wire ? CCFD_WIRE_ROW_BYTES / 4 - 1 : CCFD_N_FEATURES - 1;

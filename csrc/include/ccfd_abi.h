@@ -10,8 +10,9 @@
 extern "C" {
 #endif
 
-// CCFD_MODEL_FOREST: general (non-oblivious) tree ensembles, f32 rows, launch path only;
-// gbdt_trees / gbdt_depth carry its tree count and maximum depth (models/forest.py).
+// CCFD_MODEL_FOREST: general (non-oblivious) tree ensembles, launch path only: f32 rows ('FRS1'
+// blob) or G32 / G20 rows ('FRB1' blob, packed against the rows' bin table); gbdt_trees /
+// gbdt_depth carry its tree count and maximum depth (models/forest.py).
 enum ccfd_model_kind { CCFD_MODEL_LR = 0, CCFD_MODEL_MLP = 1, CCFD_MODEL_GBDT = 2, CCFD_MODEL_FOREST = 3 };
 
 // Cumulative u64 counter slots written by the scoring kernels' epilogue (device side)
@@ -43,13 +44,13 @@ enum ccfd_counter_slot {
 #define CCFD_ARG_FENCE_COHERENT 1   // outputs live in fine-grained pinned memory (informational)
 #define CCFD_ARG_WIRE_W64 2           // x holds W64 rows (64 B: bf16 V1..V28, f32 Time, f32 Amount)
 #define CCFD_WIRE_ROW_BYTES 64
-// G32 rows (GBDT only, 32 B): byte j < 30 = bin of feature j against the model's split
+// G32 rows (GBDT and forest models, 32 B): byte j < 30 = bin of feature j against the model's split
 // table (#edges_j < x_j, so `x_j > thr` == `bin_j > k(thr)` exactly), byte 30 = amount
 // bucket (K6), byte 31 = bin-table stamp (1..255; rows encoded for another table are
 // counted in CCFD_CNT_WIRE_STALE and not scored).  Amount itself stays host-side.
 #define CCFD_ARG_WIRE_G32 4
 #define CCFD_G32_ROW_BYTES 32
-// G20 rows (GBDT only, 20 B; flags carry WIRE_G32 | WIRE_G20): the same bins packed 5 bits
+// G20 rows (GBDT and forest models, 20 B; flags carry WIRE_G32 | WIRE_G20): the same bins packed 5 bits
 // each for bin tables of <= 31 edges per feature -- bits [5j, 5j+5) = bin of feature j,
 // bits [150, 154) = amount bucket, bits [154, 160) = bin-table stamp (1..63).  Little-endian
 // bit order over the 5 dwords of the row.  0.625x the bytes of a G32 row, equally exact.
@@ -347,7 +348,7 @@ typedef struct ccfd_engine_config {
   int32_t flag_capacity;       // flagged-transaction ring capacity (records)
   int32_t exec_mode;           // 0 = one fused launch per micro-batch, 1 = persistent kernel
   int32_t persist_grid;        // workgroups of the persistent kernel (0 = 256)
-  int32_t wire;                // 0 = f32 rows [30]; 1 = W64 rows (64 B); 2 = G32 rows (32 B, GBDT); 3 = G20 (20 B, GBDT)
+  int32_t wire;                // 0 = f32 rows [30]; 1 = W64 rows (64 B); 2 = G32 rows (32 B, GBDT / forest); 3 = G20 (20 B, GBDT / forest)
   int32_t coalesce;            // launch mode: up to this many ready micro-batches per launch (<= 8)
   int32_t persist_items;       // persistent MLP on W64 rows: 0 = env (CCFD_PERSIST_PIPE), 1 = claimed
                                // 512-row items (throughput), 2 = pipelined 128-row items (latency)

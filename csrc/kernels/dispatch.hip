@@ -13,6 +13,7 @@ int launch_lr_multi(const ccfd_multi_args& m, hipStream_t s);
 int launch_gbdt(const ccfd_score_args& a, hipStream_t s);
 int launch_gbdt_g32(const ccfd_score_args& a, hipStream_t s);
 int launch_forest(const ccfd_score_args& a, hipStream_t s);
+int launch_forest_bins(const ccfd_score_args& a, hipStream_t s);
 
 thread_local std::string g_last_error;
 void set_error(const std::string& e) { g_last_error = e; }
@@ -27,16 +28,25 @@ int ccfd_score_launch(const ccfd_score_args* a, void* stream) {
   if (a == nullptr || a->blob == nullptr || a->x == nullptr) { set_error("null argument"); return -1; }
   if (a->n < 0) { set_error("n < 0"); return -1; }
   if (a->n == 0) return 0;
-  if (a->model == CCFD_MODEL_FOREST && (a->flags & (CCFD_ARG_WIRE_W64 | CCFD_ARG_WIRE_G32 | CCFD_ARG_WIRE_G20))) {
-    set_error("forest kernel: f32 rows only (no W64 / G32 / G20 rows)");
+  if (a->model == CCFD_MODEL_FOREST && (a->flags & CCFD_ARG_WIRE_W64)) {
+    set_error("forest kernels: f32, G32 or G20 rows (no W64 rows)");
     return -3;
   }
   if (a->flags & CCFD_ARG_WIRE_G32) {
-    if (a->model != CCFD_MODEL_GBDT) { set_error("G32 rows: GBDT kernel only"); return -3; }
+    if (a->model != CCFD_MODEL_GBDT && a->model != CCFD_MODEL_FOREST) {
+      set_error("G32 rows: GBDT and forest kernels only");
+      return -3;
+    }
     const bool g20 = (a->flags & CCFD_ARG_WIRE_G20) != 0;     // dword loads: 4-byte aligned rows
     if (reinterpret_cast<uintptr_t>(a->x) & (g20 ? 3 : 15)) {
       set_error(g20 ? "G20 rows must be 4-byte aligned" : "G32 rows must be 16-byte aligned");
       return -3;
+    }
+    if (a->model == CCFD_MODEL_FOREST) {
+      const int rc = launch_forest_bins(*a, reinterpret_cast<hipStream_t>(stream));
+      if (rc != 0 && rc != -2)          // -2: blob refused before any launch; message already set
+        set_error(std::string("kernel launch failed: ") + hipGetErrorString(hipGetLastError()));
+      return rc;
     }
     const int rc = launch_gbdt_g32(*a, reinterpret_cast<hipStream_t>(stream));
     if (rc == -2) set_error("G32 launch: bad tree shape (depth 1..8, leaf tables <= 64 KB)");

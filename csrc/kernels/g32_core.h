@@ -1,7 +1,8 @@
 // Shared device code of the binned-row (G32 / G20) oblivious-GBDT kernels: score_gbdt_g32.hip
 // (one launch per micro-batch), score_gbdt_g32_persist.hip (persistent: claimed and pipelined
 // items) and score_gbdt_shadow.hip (a challenger beside the champion, launch and persistent).
-// Separate translation units so the many (depth x rules x leaf-placement) instantiations
+// The general-tree kernel on binned rows (score_forest_bins.hip) takes the row formats and the
+// scored-row epilogue from here.  Separate translation units so the many (depth x rules x leaf-placement) instantiations
 // compile in parallel.  Here: the row formats (fetch, transpose, lift), the tree walk, the
 // view of a GBB1 blob (G32Model), and what every kernel does with a scored row (g32_row_epilogue,
 // g32_wave_commit / g32_item_commit).
@@ -259,14 +260,18 @@ struct G32RowOut {
 // (stale rows -- meta = bucket | stamp << 8 of another bin table -- are counted, not scored),
 // route by threshold or proba-only rules (kR), proba / route outputs, the workgroup's amount
 // histogram and the wave's counts.  The flag list stays with the caller (emit_flagged and
-// persist_emit_flagged are different protocols).
-template <bool kR>
+// persist_emit_flagged are different protocols).  kProba: `acc` already is the row's
+// probability (the general-tree kernel, whose link is the blob's: score_forest_bins.hip).
+template <bool kR, bool kProba = false>
 __device__ __forceinline__ G32RowOut g32_row_epilogue(EpilogueLds& epi, G32Wave& w, const G32Model& M, unsigned meta,
                                                       float acc, int row, int n, float threshold,
                                                       const ccfd_rule_prog* rules, float* proba, uint8_t* route) {
   const bool valid = row < n;
   const bool fresh = ((meta >> 8) & 0xffu) == M.stamp;
-  const float p = fresh ? sigmoid(M.base + acc) : __builtin_nanf("");
+  float p_fresh;
+  if constexpr (kProba) p_fresh = acc;
+  else p_fresh = sigmoid(M.base + acc);
+  const float p = fresh ? p_fresh : __builtin_nanf("");
   bool fr;
   if constexpr (kR) fr = valid && fresh && rule_route(rules, p, [](int) { return 0.f; });
   else fr = valid && fresh && (p >= threshold);

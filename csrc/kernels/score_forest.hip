@@ -23,7 +23,7 @@
 #include <string>
 #include <unordered_map>
 
-#include "common.h"
+#include "forest_core.h"
 #include "gb_rows.h"
 #include "rules.h"
 
@@ -31,18 +31,7 @@ namespace ccfd {
 
 void set_error(const std::string& e);
 
-// Node-table LDS budget (mirrored by models/forest.py LDS_NODE_BYTES).  Static LDS of this
-// kernel is ~8.9 KB (xs 7.5 KB + part 1 KB + epilogue), a CU has 160 KiB: tables up to
-// ~71 KB leave room for two workgroups per CU, anything larger for one.  One workgroup per CU
-// is one wave per SIMD, which is why the walk carries several chains per lane; an LDS gather at
-// that occupancy still beats an L2 gather (~10x the latency) at full occupancy, so the
-// budget is everything one workgroup can take: 144 KiB = 18432 nodes (a 100 x depth-6
-// complete ensemble is 12700).  Smaller tables allocate only what they need and keep the
-// higher occupancy.
-constexpr int kNodeLdsBytes = 144 * 1024;
-constexpr int kFrStaticLds = 9 * 1024;        // upper bound of the static LDS above
-constexpr int kFrMaxDepth = 64;
-constexpr int kFrMaxNodes = 1 << 24;          // child index field: 24 bits
+constexpr int kFrStaticLds = 9 * 1024;        // upper bound of this kernel's static LDS (forest_core.h)
 // Independent tree walks per lane, measured on 16 M HBM-resident rows (profiles/forest/).
 // LDS table (100 complete depth-6 trees): one workgroup per CU is one wave per SIMD and the
 // chains are what hides the LDS latency -- 4: 1.85, 8: 2.17, 16: 2.29 G rows/s.  Global table
@@ -56,17 +45,6 @@ constexpr int kFrMaxNodes = 1 << 24;          // child index field: 24 bits
 #endif
 constexpr int kIlpLds = CCFD_FOREST_ILP_LDS;
 constexpr int kIlpGlobal = CCFD_FOREST_ILP_GLOBAL;
-
-struct FrNode { unsigned w; float v; };       // w: bits 0..4 feature, bit 5 leaf, bits 8..31 left child
-
-// Node i as one 64-bit word: w in the low half, v in the high half.
-template <bool kLds>
-__device__ __forceinline__ FrNode fr_node(const uint2* __restrict__ gn, const uint2* ln, unsigned i) {
-  unsigned long long q;
-  if constexpr (kLds) q = reinterpret_cast<const unsigned long long*>(ln)[i];
-  else q = *(const CCFD_GAS unsigned long long*)(gn + i);
-  return FrNode{(unsigned)q, __uint_as_float((unsigned)(q >> 32))};
-}
 
 // Walk U trees (t0, t0 + 4, ...) of this wave for the lane's row; returns the leaf sum.
 // The step is branch-free on purpose: a leaf's feature field is 0, so its (ignored) feature
@@ -204,20 +182,11 @@ __global__ __launch_bounds__(256) void score_forest_kernel(ccfd_score_args a, in
   signal_done(a, gridDim.x);
 }
 
-// The launch needs the node count (LDS size) and re-checks the shape, both from the blob's
-// header, which lives in device memory: it is read once per blob address and cached;
-// ccfd_forest_blob_changed() drops an address whose memory was rewritten (ops/kernels.py
-// calls it for every blob it uploads).  A stale entry cannot make the kernel read out of
-// bounds -- the kernel takes T / n_nodes from the device header and compares n_nodes with
-// the LDS it was given -- it only costs the table its LDS residency.
-// The read is a blocking copy, so the first launch with a blob cannot sit inside a stream capture.
-struct FrHeader { char magic[4]; int flags, T, depth; float base; int n_nodes; int pad[10]; };
-static_assert(sizeof(FrHeader) == kHeader, "FRS1 header is 64 bytes");
-
+// The cache of blob headers of both general-tree launches (forest_core.h).
 static std::mutex g_fr_mu;
 static std::unordered_map<const void*, FrHeader> g_fr_headers;
 
-static int forest_header(const void* blob, FrHeader& h) {
+int forest_header(const void* blob, FrHeader& h) {
   std::lock_guard<std::mutex> g(g_fr_mu);
   auto it = g_fr_headers.find(blob);
   if (it != g_fr_headers.end()) { h = it->second; return 0; }
@@ -225,6 +194,16 @@ static int forest_header(const void* blob, FrHeader& h) {
   if (g_fr_headers.size() >= 256) g_fr_headers.clear();
   g_fr_headers.emplace(blob, h);
   return 0;
+}
+
+bool forest_shape_ok(const FrHeader& h, const ccfd_score_args& a) {
+  if (h.T <= 0 || a.gbdt_trees <= 0) { set_error("forest launch: no trees"); return false; }
+  if (h.depth < 0 || h.depth > kFrMaxDepth || a.gbdt_depth < 0 || a.gbdt_depth > kFrMaxDepth) {
+    set_error("forest launch: tree depth outside 0..64");
+    return false;
+  }
+  if (h.n_nodes < h.T || h.n_nodes >= kFrMaxNodes) { set_error("forest launch: node count outside [T, 2^24)"); return false; }
+  return true;
 }
 
 template <bool kContig, bool kR>
@@ -244,13 +223,13 @@ int launch_forest(const ccfd_score_args& a, hipStream_t s) {
   if (a.n <= 0) return 0;
   FrHeader h;
   if (forest_header(a.blob, h) != 0) { set_error("forest launch: cannot read the blob header"); return -2; }
-  if (std::memcmp(h.magic, "FRS1", 4) != 0) { set_error("forest launch: not an FRS1 blob"); return -2; }
-  if (h.T <= 0 || a.gbdt_trees <= 0) { set_error("forest launch: no trees"); return -2; }
-  if (h.depth < 0 || h.depth > kFrMaxDepth || a.gbdt_depth < 0 || a.gbdt_depth > kFrMaxDepth) {
-    set_error("forest launch: tree depth outside 0..64");
+  if (std::memcmp(h.magic, "FRS1", 4) != 0) {
+    set_error(std::memcmp(h.magic, "FRB1", 4) == 0
+                  ? "forest launch: an FRB1 blob scores G32 / G20 rows, these are f32 rows (pack without bins=)"
+                  : "forest launch: not an FRS1 blob");
     return -2;
   }
-  if (h.n_nodes < h.T || h.n_nodes >= kFrMaxNodes) { set_error("forest launch: node count outside [T, 2^24)"); return -2; }
+  if (!forest_shape_ok(h, a)) return -2;
   const bool contig = a.ld == kF && (reinterpret_cast<uintptr_t>(a.x) & 15) == 0;
   const int lds_nodes = (size_t)h.n_nodes * 8 <= (size_t)kNodeLdsBytes ? h.n_nodes : 0;
   // ~one wave of workgroups: as many per CU as the LDS footprint allows (<= 4: 16 waves / CU)

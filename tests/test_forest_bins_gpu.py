@@ -1,0 +1,355 @@
+"""The general-tree kernel on binned rows (csrc/kernels/score_forest_bins.hip, blob 'FRB1')
+against the CPU oracle ``TreeEnsemble.predict_proba`` on the unbinned rows: G32 and G20 rows,
+LDS-resident and global-memory node tables, every chain-group tail, every row-count edge of
+the 64-row chunking, both links, stale stamps, rules, refusals, and the streaming engine in
+launch mode on a binned partition log with a hot swap."""
+import numpy as np
+import pytest
+import torch
+
+from ccfd_demo_summit_amd.contracts.transaction import decode_g20_bins
+from ccfd_demo_summit_amd.data import generate
+from ccfd_demo_summit_amd.models import TreeEnsemble, build_model
+from ccfd_demo_summit_amd.models.forest import LDS_NODE_BYTES, NODE_BYTES
+
+pytestmark = pytest.mark.gpu
+
+N_DATA = 70001
+
+
+def proba_bound(m: TreeEnsemble) -> float:
+    """fp32 bound on a probability (tests/test_forest_gpu.py, derived in tests/test_forest_cpu.py):
+    T float32 roundings of magnitude <= |base| + sum_t max|leaf_t| in the sum, times the
+    sigmoid's slope 1/4.  The binned walk selects the f32 walk's leaves exactly, so the bound
+    is the f32 kernel's."""
+    return 0.25 * m.n_trees * 2.0 ** -23 * (abs(m.base) + m.leaf_abs_max().sum()) + 1e-6
+
+
+def _bucket(rows: np.ndarray) -> np.ndarray:
+    """The amount bucket a binned row carries (G32: byte 30; G20: bits 150..153)."""
+    return (rows if rows.shape[1] == 32 else decode_g20_bins(rows))[:, 30]
+
+
+def _check_counters(cnt, p, route, rows, stale=0):
+    """tests/test_forest_gpu.py _check_counters, with the amount histogram taken from the rows'
+    bucket byte; a stale row counts as incoming / standard and adds no probability."""
+    cnt = cnt.cpu().numpy()
+    n = len(p)
+    assert cnt[0] == n
+    assert cnt[1] == route.sum()
+    assert cnt[2] == n - route.sum()
+    assert abs(int(cnt[3]) - int(np.nansum(np.round(p.astype(np.float64) * 1e6)))) <= n
+    assert cnt[4] == stale
+    b = _bucket(rows)
+    np.testing.assert_array_equal(cnt[8:22], np.bincount(b[route == 0], minlength=14))
+    np.testing.assert_array_equal(cnt[24:38], np.bincount(b[route == 1], minlength=14))
+
+
+def _concat(parts):
+    feat, value, child, leaf, root, off = [], [], [], [], [], 0
+    for m in parts:
+        feat.append(m.feat); value.append(m.value); leaf.append(m.leaf)
+        child.append(m.child + off); root.append(m.root + off)
+        off += m.n_nodes
+    return TreeEnsemble(np.concatenate(feat), np.concatenate(value), np.concatenate(child), np.concatenate(leaf),
+                        np.concatenate(root), parts[0].base, parts[0].link)
+
+
+def _chain(depth, X, seed):
+    """One tree of depth ``depth``: every right child splits again, every left child is a
+    leaf; thresholds at the 15 % quantile so that rows spread over the whole chain."""
+    rng = np.random.default_rng(seed)
+    n = depth
+    feat = np.array([1] + [0, 1] * (n - 1) + [0, 0])
+    leaf = np.array([False] + [True, False] * (n - 1) + [True, True])
+    child = np.array([1] + [0, 0] * (n - 1) + [0, 0])
+    child[2:2 * n - 1:2] = 3 + 2 * np.arange(n - 1)
+    inner = np.flatnonzero(~leaf)
+    feat[inner] = rng.integers(0, 30, inner.size)
+    value = (rng.standard_normal(feat.size) * 0.3).astype(np.float32)
+    value[inner] = [np.quantile(X[:, f], 0.15) for f in feat[inner]]
+    return TreeEnsemble(feat, value, child, leaf, [0])
+
+
+@pytest.fixture(scope="module")
+def data():
+    X, y = generate(N_DATA, seed=11)
+    X[3, 5] = np.nan          # NaN goes left on both sides (bin 0); +-inf land in the end bins
+    X[4, 2] = np.inf
+    X[5, 7] = -np.inf
+    return X, y
+
+
+def _rows_of(data, n):
+    """The first n rows; past the generated ones they repeat with an odd shift, so that the
+    chunks of a large batch differ."""
+    X = data[0]
+    return X[:n] if n <= N_DATA else X[(np.arange(n) * 3 + np.arange(n) // N_DATA) % N_DATA]
+
+
+@pytest.fixture(scope="module")
+def ensembles(data):
+    from sklearn.ensemble import GradientBoostingClassifier, RandomForestClassifier
+    from ccfd_demo_summit_amd.models.sklearn_import import from_sklearn
+    X, y = data[0][6:4006], data[1][6:4006]
+    one_leaf = TreeEnsemble([0], [0.375], [0], [True], [0])
+    small = build_model("gbdt", seed=5, X_ref=X, gbdt_trees=10, gbdt_depth=4, calibrate_rate=0.05)
+    e = {
+        "t1": TreeEnsemble.random_init(1, 6, 0.2, 1, X),
+        "t3": TreeEnsemble.random_init(3, 5, 0.2, 2, X),          # tail groups of 2 and 1
+        "t5": TreeEnsemble.random_init(5, 7, 0.25, 3, X),         # tail groups of 4 and 1
+        "t21": TreeEnsemble.random_init(21, 6, 0.2, 9, X),        # two full groups of 8, then 4 and 1
+        "leaf_only_among": _concat([TreeEnsemble.random_init(2, 4, 0.2, 4, X), one_leaf,
+                                    TreeEnsemble.random_init(3, 4, 0.2, 5, X)]),
+        "stumps": TreeEnsemble.random_init(9, 1, 0.0, 6, X),
+        "chain24": _concat([_chain(24, X, 7), TreeEnsemble.random_init(2, 3, 0.2, 8, X)]),
+        "lds_below": TreeEnsemble.random_init(64, 12, 0.295, 3, X),
+        "lds_above": TreeEnsemble.random_init(64, 12, 0.3, 4, X),
+        "global8": TreeEnsemble.random_init(8, 12, 0.0, 10, X),   # 8 complete depth-12 trees: 3.5 LDS budgets
+        "rf_identity": from_sklearn(RandomForestClassifier(n_estimators=5, random_state=0).fit(X, y)),
+        "gb_sigmoid": from_sklearn(GradientBoostingClassifier(n_estimators=10, max_depth=3, random_state=3).fit(X, y)),
+        "wide": TreeEnsemble.random_init(8, 8, 0.0, 2),           # N(0,1) thresholds: > 31 a feature, G32 only
+        "oblivious_padded": TreeEnsemble.from_oblivious(small.padded(n_trees=12, depth=5)),
+    }
+    assert e["stumps"].depth == 1 and e["chain24"].depth == 24 and e["leaf_only_among"].tree_depth[2] == 0
+    assert 0.95 * LDS_NODE_BYTES < e["lds_below"].n_nodes * NODE_BYTES <= LDS_NODE_BYTES
+    assert LDS_NODE_BYTES < e["lds_above"].n_nodes * NODE_BYTES < 1.05 * LDS_NODE_BYTES
+    assert e["global8"].n_nodes * NODE_BYTES > 3 * LDS_NODE_BYTES
+    assert e["rf_identity"].link == "identity" and e["gb_sigmoid"].link == "sigmoid"
+    assert not e["wide"].bin_spec().fits_g20
+    assert np.isnan(e["oblivious_padded"].value[~e["oblivious_padded"].leaf]).any()
+    return e
+
+
+_oracle_cache = {}
+
+
+def _oracle(name, m, data, n):
+    key = (name, n)
+    if key not in _oracle_cache:
+        _oracle_cache[key] = m.predict_proba(_rows_of(data, n))
+    return _oracle_cache[key]
+
+
+# The launch's grid cap (score_forest_bins.hip launch_forest_bins): one wave per 64-row chunk,
+# four waves a workgroup, at most 256 * per_cu workgroups with
+# per_cu = min(4, 160 KiB / (8384 B of tiles and epilogue + the LDS node table)).
+# Past 256 * per_cu * 4 * 64 rows a wave walks several chunks, the next one prefetched.
+def _grid_cap_rows(m: TreeEnsemble) -> int:
+    table = m.n_nodes * NODE_BYTES if m.n_nodes * NODE_BYTES <= LDS_NODE_BYTES else 0
+    per_cu = min(4, max(1, (160 * 1024) // (8384 + table)))
+    return 256 * per_cu * 4 * 64
+
+
+NAMES = ["t1", "t3", "t5", "t21", "leaf_only_among", "stumps", "chain24", "lds_below", "lds_above", "global8",
+         "rf_identity", "gb_sigmoid", "wide", "oblivious_padded"]
+# every ensemble at 65 rows on both formats; every row-count edge on a small LDS-resident
+# ensemble and on a global-memory one; and (test_past_a_full_grid) one size past the grid cap
+CASES = [(k, 65, f) for k in NAMES for f in ("g32", "g20") if (k, f) != ("wide", "g20")] + \
+        [(k, n, f) for k in ("t5", "global8") for n in (1, 63, 64, 257, 4097) for f in ("g32", "g20")]
+
+
+def _score_and_check(gpu, data, ensembles, name, n, fmt):
+    from ccfd_demo_summit_amd.ops.kernels import DeviceModel, new_counters, score
+    m = ensembles[name]
+    X = _rows_of(data, n)
+    dm = DeviceModel(m, gpu, bins=fmt)
+    assert dm.row_format == fmt and (dm.trees, dm.depth) == (m.n_trees, m.depth)
+    rows = dm.bins.encode(X)
+    cnt = new_counters(gpu)
+    p, r = score(dm, torch.from_numpy(rows).to(gpu), 0.5, counters=cnt)
+    torch.cuda.synchronize()
+    p, r = p.cpu().numpy(), r.cpu().numpy()
+    err = np.abs(p.astype(np.float64) - _oracle(name, m, data, n)).max()
+    print(f"{name} {fmt} n={n}: nodes {m.n_nodes}, max |p - oracle| = {err:.3e}, bound {proba_bound(m):.3e}")
+    assert err <= proba_bound(m)
+    np.testing.assert_array_equal(r, (p >= 0.5).astype(np.uint8))
+    _check_counters(cnt, p, r, rows)
+
+
+@pytest.mark.parametrize("name,n,fmt", CASES)
+def test_forest_bins_kernel_matches_oracle(gpu, data, ensembles, name, n, fmt):
+    _score_and_check(gpu, data, ensembles, name, n, fmt)
+
+
+@pytest.mark.parametrize("name,fmt", [("lds_below", "g32"), ("lds_below", "g20"), ("global8", "g32"), ("global8", "g20")])
+def test_past_a_full_grid(gpu, data, ensembles, name, fmt):
+    """17 chunks and one row past the grid cap: 17 waves walk a second chunk, fetched while they
+    walked the first, and the last chunk holds one row."""
+    cap = _grid_cap_rows(ensembles[name])
+    assert cap == (65536 if name == "lds_below" else 262144)
+    _score_and_check(gpu, data, ensembles, name, cap + 16 * 64 + 1, fmt)
+
+
+def test_same_routes_as_the_f32_forest_kernel_and_the_oblivious_g32_kernel(gpu, data):
+    from ccfd_demo_summit_amd.ops.kernels import DeviceModel, score
+    X = data[0][:4097]
+    g = build_model("gbdt", seed=3, X_ref=data[0][6:5006], calibrate_rate=0.05)     # past the NaN / inf rows
+    f = TreeEnsemble.from_oblivious(g)
+    dg, db, df = DeviceModel(g, gpu, bins=True), DeviceModel(f, gpu, bins="g32"), DeviceModel(f, gpu)
+    assert db.bins.stamp == dg.bins.stamp                      # the same thresholds, the same table
+    rows = torch.from_numpy(dg.bins.encode(X)).to(gpu)
+    pb, rb = score(db, rows, 0.5)
+    pg, rg = score(dg, rows, 0.5)
+    pf, rf = score(df, torch.from_numpy(X).to(gpu), 0.5)
+    torch.cuda.synchronize()
+    pb, rb, pg, rg, pf, rf = (t.cpu().numpy() for t in (pb, rb, pg, rg, pf, rf))
+    b = proba_bound(f)
+    assert np.abs(pb.astype(np.float64) - f.predict_proba(X)).max() <= b
+    assert np.abs(pb.astype(np.float64) - pf).max() <= 2 * b
+    assert np.abs(pb.astype(np.float64) - pg).max() <= 2 * b
+    clear = np.abs(pb - 0.5) > 2 * b
+    assert clear.sum() > 4000 and 0 < rb.sum() < 4097
+    np.testing.assert_array_equal(rb[clear], rf[clear])
+    np.testing.assert_array_equal(rb[clear], rg[clear])
+
+
+@pytest.mark.parametrize("fmt", ["g32", "g20"])
+def test_stale_stamp_rows_counted_not_scored(gpu, data, ensembles, fmt):
+    from ccfd_demo_summit_amd.ops.kernels import DeviceModel, new_counters, score
+    X = data[0][:4097]
+    for name in ("gb_sigmoid", "lds_above"):
+        m = ensembles[name]
+        dm = DeviceModel(m, gpu, bins=fmt)
+        enc = dm.bins.encode(X)
+        if fmt == "g32":                                     # another table's stamp: byte 31
+            enc[100:200, 31] = (enc[100:200, 31] % 255) + 1
+        else:                                                # bits 154..159: the top six of byte 19
+            other = (enc[100:200, 19] >> 2) % 63 + 1
+            enc[100:200, 19] = (enc[100:200, 19] & 3) | (other << 2).astype(np.uint8)
+        enc[300, :] = 0                                      # zeroed memory is never fresh
+        cnt = new_counters(gpu)
+        p, r = score(dm, torch.from_numpy(enc).to(gpu), 0.5, counters=cnt)
+        torch.cuda.synchronize()
+        p, r = p.cpu().numpy(), r.cpu().numpy()
+        stale = np.zeros(4097, bool)
+        stale[100:200] = True
+        stale[300] = True
+        assert np.isnan(p[stale]).all() and not r[stale].any()
+        assert np.abs(p[~stale].astype(np.float64) - m.predict_proba(X)[~stale]).max() <= proba_bound(m)
+        np.testing.assert_array_equal(r[~stale], (p[~stale] >= 0.5).astype(np.uint8))
+        _check_counters(cnt, p, r, enc, stale=101)
+
+
+@pytest.mark.parametrize("fmt", ["g32", "g20"])
+def test_proba_rules_route_and_feature_rules_are_refused(gpu, data, ensembles, fmt):
+    from ccfd_demo_summit_amd.ops.kernels import DeviceModel, DeviceRules, new_counters, score
+    from ccfd_demo_summit_amd.router.rules import RuleSet
+    X = data[0][:4097]
+    m = ensembles["t21"]
+    dm = DeviceModel(m, gpu, bins=fmt)
+    enc = dm.bins.encode(X)
+    rows = torch.from_numpy(enc).to(gpu)
+    rs = RuleSet.parse("when proba >= 0.6 then fraud\nwhen proba < 0.4 then fraud\notherwise standard")
+    assert not rs.feature_vars()
+    cnt = new_counters(gpu)
+    p, r = score(dm, rows, 0.5, counters=cnt, rules=DeviceRules(rs, gpu))
+    torch.cuda.synchronize()
+    p, r = p.cpu().numpy(), r.cpu().numpy()
+    assert np.abs(p.astype(np.float64) - m.predict_proba(X)).max() <= proba_bound(m)
+    want = rs.evaluate(p)
+    assert 0 < want.sum() < 4097
+    np.testing.assert_array_equal(r, want)
+    _check_counters(cnt, p, r, enc)
+    with pytest.raises(ValueError, match="proba_1"):
+        score(dm, rows, 0.5, rules=DeviceRules(RuleSet.parse("when amount > 100 then fraud\notherwise standard"), gpu))
+
+
+def test_refusals(gpu, data, ensembles):
+    from ccfd_demo_summit_amd.engine import StreamEngine
+    from ccfd_demo_summit_amd.ops.kernels import DeviceModel, score
+    m = ensembles["t5"]
+    dm = DeviceModel(m, gpu, bins="g32")
+    enc = dm.bins.encode(data[0][:65])
+    buf = torch.zeros(65 * 32 + 16, dtype=torch.uint8, device=gpu)
+    off = 8 + (-buf.data_ptr()) % 16                            # 8 bytes past a 16-byte boundary
+    x = buf[off:off + 65 * 32].view(65, 32)
+    x.copy_(torch.from_numpy(enc))
+    assert x.data_ptr() % 16 == 8 and x.is_contiguous()
+    with pytest.raises(RuntimeError, match="16-byte aligned"):
+        score(dm, x, 0.5)
+    # an FRS1 blob (f32 thresholds) handed over as a model for G32 rows
+    f32 = DeviceModel(m, gpu)
+    wrong = DeviceModel.from_blob("forest", f32.blob, m.n_trees, m.depth, bins=dm.bins)
+    with pytest.raises(RuntimeError, match="FRS1"):
+        score(wrong, torch.from_numpy(enc).to(gpu), 0.5)
+    # ... and an FRB1 blob as a model for f32 rows
+    wrong = DeviceModel.from_blob("forest", dm.blob, m.n_trees, m.depth)
+    with pytest.raises(RuntimeError, match="FRB1"):
+        score(wrong, torch.from_numpy(data[0][:65]).to(gpu), 0.5)
+    torch.cuda.synchronize()
+    with pytest.raises(RuntimeError, match="forest"):       # a host-side check at construction, before any launch
+        StreamEngine(dm, batch=1024, depth=2, streams=1, input_mode="zerocopy", output_mode="zerocopy",
+                     exec_mode="persistent")
+    with pytest.raises(ValueError, match="f32 rows"):
+        DeviceModel(m, gpu, bins=True)
+    with pytest.raises(ValueError, match="f32 rows"):
+        DeviceModel(m, gpu, wire=True)
+    with pytest.raises(ValueError, match="split thresholds > 31"):
+        DeviceModel(ensembles["wide"], gpu, bins="g20")
+
+
+@pytest.mark.parametrize("fmt,input_mode", [("g32", "zerocopy"), ("g20", "zerocopy"), ("g32", "dma")])
+def test_stream_engine_launch_mode_on_a_binned_log_and_swap(gpu, data, ensembles, fmt, input_mode):
+    from ccfd_demo_summit_amd.engine import PartitionLog, StreamEngine
+    from ccfd_demo_summit_amd.ops.kernels import DeviceModel
+    B = 1000
+    X = data[0][:5 * B]
+    a, b = ensembles["t21"], ensembles["t5"]
+    assert (a.n_nodes, a.n_trees) != (b.n_nodes, b.n_trees)
+    table = _concat([a, b]).bin_spec(8 if fmt == "g32" else 5)      # the live table holds both models' thresholds
+    dm = DeviceModel(a, gpu, bins=table)
+    assert dm.row_format == fmt
+    eng = StreamEngine(dm, batch=B, depth=4, streams=2, input_mode=input_mode, output_mode="zerocopy",
+                       threshold=0.5, exec_mode="launch")
+    log = PartitionLog.from_arrays(X, ids=np.arange(X.shape[0], dtype=np.uint64) + 7, bins=dm.bins)
+    other = None
+    try:
+        eng.add_log(0, log)
+        p, r = eng.score(X)
+        ref = a.predict_proba(X)
+        assert np.abs(p.astype(np.float64) - ref).max() <= proba_bound(a)
+        np.testing.assert_array_equal(r, (p >= 0.5).astype(np.uint8))
+        st = eng.pump(5)
+        assert st.rows == 5 * B and st.dev_batches == 5
+        fl = eng.drain_flagged()
+        got = np.zeros(5 * B, bool)
+        got[(fl["tx_id"] - 7).astype(np.int64)] = True
+        assert 0 < got.sum() < 5 * B and len(fl) == got.sum()
+        np.testing.assert_array_equal(got, r.astype(bool))             # the same kernel on the same rows
+        clear = np.abs(ref - 0.5) > proba_bound(a)
+        np.testing.assert_array_equal(got[clear], ref[clear] >= 0.5)
+        np.testing.assert_allclose(fl["amount"], X[(fl["tx_id"] - 7).astype(np.int64), 29])
+        eng.swap_model(DeviceModel(b, gpu, bins=eng.bins))
+        p, r = eng.score(X)
+        assert np.abs(p.astype(np.float64) - b.predict_proba(X)).max() <= proba_bound(b)
+        np.testing.assert_array_equal(r, (p >= 0.5).astype(np.uint8))
+        with pytest.raises(ValueError, match="bin table"):         # b's own table is another one
+            eng.swap_model(DeviceModel(b, gpu, bins=fmt))
+        other = PartitionLog.from_arrays(X[:B], bins=b.bin_spec(8 if fmt == "g32" else 5))
+        with pytest.raises(ValueError, match="bin table"):
+            eng.add_log(1, other)
+    finally:
+        eng.close()
+        log.free()
+        if other is not None:
+            other.free()
+
+
+def test_broadcast_model_carries_a_binned_forest(gpu, data, ensembles):
+    """parallel.dp.broadcast_model: a forest goes out as an FRB1 blob with its bin table, and an
+    ensemble with more than 31 thresholds on a feature widens from G20 to G32 rows."""
+    from ccfd_demo_summit_amd.ops.kernels import score
+    from ccfd_demo_summit_amd.parallel import broadcast_model, init_distributed
+    X = data[0][:4097]
+    ctx = init_distributed()
+    for name, fmt in (("rf_identity", "g32"), ("gb_sigmoid", "g20")):
+        m = ensembles[name]
+        dm = broadcast_model(ctx, m, "forest", fmt)
+        assert dm.kind == "forest" and dm.row_format == fmt and dm.bins.stamp == m.bin_spec(dm.bins.bits).stamp
+        p, _ = score(dm, torch.from_numpy(dm.bins.encode(X)).to(gpu))
+        torch.cuda.synchronize(gpu)
+        assert np.abs(p.cpu().numpy().astype(np.float64) - _oracle(name, m, data, 4097)).max() <= proba_bound(m)
+    with pytest.warns(UserWarning, match="G20 rows impossible"):
+        dm = broadcast_model(ctx, ensembles["wide"], "forest", "g20")
+    assert dm.row_format == "g32"
