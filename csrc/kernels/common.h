@@ -44,6 +44,12 @@ inline auto dispatch_depth(int depth, F&& f) {
   }
 }
 
+// Runtime flag -> compile-time bool: f(std::true_type{}) or f(std::false_type{}).
+template <class F>
+inline auto dispatch_bool(bool v, F&& f) {
+  return v ? f(std::true_type{}) : f(std::false_type{});
+}
+
 // Row loads and output stores through the GLOBAL address space.  A generic pointer (every
 // pointer read from a descriptor or struct) compiles to FLAT instructions, and a FLAT
 // load / store counts on LGKM_CNT as well as VM_CNT: each `s_waitcnt lgkmcnt(0)` that an

@@ -314,23 +314,6 @@ __device__ __forceinline__ void g32_item_commit(EpilogueLds& epi, G32Wave& w, un
   w = G32Wave{};
 }
 
-// A persistent kernel's work item `it` (C items a micro-batch, `chunks` 64-row chunks an item
-// over kW waves) as wave `wave` sees it: the wave scores chunks c0, c0 + kW, ...
-struct G32Item {
-  int slot, n, c0;
-  const unsigned char* xb;
-};
-
-// `stamp`: this thread stamps the micro-batch's start (K7) if the item is its first.
-__device__ __forceinline__ G32Item g32_item(const ccfd_persist_args& a, const ccfd_persist_desc& d, unsigned long long it,
-                                            int C, int chunks, int wave, bool stamp) {
-  const int item = (int)(it % (unsigned long long)C);
-  const int slot = (int)(d.seq % (unsigned long long)a.ring);
-  if (item == 0 && stamp)
-    __hip_atomic_store(&a.dev->tstart[slot], wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  return G32Item{slot, d.n, item * chunks + wave, reinterpret_cast<const unsigned char*>(d.x)};
-}
-
 // read per launch, so in-process sweeps can vary it
 inline int g32_env(const char* name, int dflt, int lo, int hi) {
   const char* e = getenv(name);

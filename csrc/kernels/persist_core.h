@@ -106,20 +106,35 @@ __device__ __forceinline__ void persist_read_desc(const ccfd_persist_args& a, un
   sdesc.seq = b;
 }
 
-// Thread 0: wait until claimed item `item`'s micro-batch is posted, then read its descriptor;
-// returns 1 (and reads nothing) when the host stopped the kernel instead.
-__device__ __forceinline__ int persist_wait_item(const ccfd_persist_args& a, int C, unsigned long long& posted_cache,
-                                                 unsigned long long item, ccfd_persist_desc& sdesc) {
-  const unsigned long long b = item / (unsigned long long)C;
+// Thread 0: poll the device mirror until micro-batch b is posted; returns 1 when the host
+// stopped the kernel instead.  Relaxed polls: the acquire fence in persist_read_desc runs once
+// the batch is posted.  kFarNaps (static-item pipelines): a worker waiting for a batch >= 2
+// batches ahead of the posted count naps ~1 us, so idle workers do not hammer the `posted` word.
+template <bool kFarNaps>
+__device__ __forceinline__ int persist_wait_posted(const ccfd_persist_args& a, unsigned long long b,
+                                                   unsigned long long& posted_cache) {
   unsigned sleep_n = 1;
   while (posted_cache <= b) {
-    // relaxed poll; the acquire fence in persist_read_desc runs once the batch is posted
     posted_cache = __hip_atomic_load(&a.dev->posted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (posted_cache > b) break;
     if (__hip_atomic_load(&a.dev->stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return 1;
-    for (unsigned k = 0; k < sleep_n; ++k) __builtin_amdgcn_s_sleep(1);
-    sleep_n = sleep_n < 8 ? sleep_n * 2 : 8;
+    if (kFarNaps && b - posted_cache >= 2) {
+      for (int k = 0; k < 4; ++k) __builtin_amdgcn_s_sleep(8);
+    } else {
+      for (unsigned k = 0; k < sleep_n; ++k) __builtin_amdgcn_s_sleep(1);
+      sleep_n = sleep_n < 8 ? sleep_n * 2 : 8;
+    }
   }
+  return 0;
+}
+
+// Thread 0: wait until item `item`'s micro-batch is posted, then read its descriptor; returns 1
+// (and reads nothing) when the host stopped the kernel instead.
+template <bool kFarNaps>
+__device__ __forceinline__ int persist_wait_item(const ccfd_persist_args& a, int C, unsigned long long& posted_cache,
+                                                 unsigned long long item, ccfd_persist_desc& sdesc) {
+  const unsigned long long b = item / (unsigned long long)C;
+  if (persist_wait_posted<kFarNaps>(a, b, posted_cache)) return 1;
   persist_read_desc(a, b, sdesc);
   return 0;
 }
@@ -130,14 +145,12 @@ __device__ __forceinline__ void persist_claim(const ccfd_persist_args& a, int C,
                                               ccfd_persist_desc& sdesc, unsigned long long& s_item, int& s_cmd) {
   const unsigned long long item =
       __hip_atomic_fetch_add(&a.dev->work_next, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  s_cmd = persist_wait_item(a, C, posted_cache, item, sdesc);
+  s_cmd = persist_wait_item<false>(a, C, posted_cache, item, sdesc);
   s_item = item;
 }
 
-// Static-item pipelines (persist_pipe_kernel, persist_gbdt_pipe_kernel): thread 0 reads item
-// `item`'s descriptor if its micro-batch is already posted (1) or reports that it is not yet (0)
-// without waiting; persist_wait_far waits for it (napping longer when it is >= 2 batches
-// ahead) and returns 1 when the host stopped the kernel instead.
+// Static-item pipelines: thread 0 reads item `item`'s descriptor if its micro-batch is already
+// posted (1) or reports that it is not yet (0) without waiting.
 __device__ __forceinline__ int persist_try_item(const ccfd_persist_args& a, int C, unsigned long long& posted_cache,
                                                 unsigned long long item, ccfd_persist_desc& sdesc) {
   const unsigned long long b = item / (unsigned long long)C;
@@ -148,23 +161,28 @@ __device__ __forceinline__ int persist_try_item(const ccfd_persist_args& a, int 
   return 1;
 }
 
-__device__ __forceinline__ int persist_wait_far(const ccfd_persist_args& a, int C, unsigned long long& posted_cache,
-                                                unsigned long long item, ccfd_persist_desc& sdesc) {
-  const unsigned long long b = item / (unsigned long long)C;
-  unsigned sleep_n = 1;
-  while (posted_cache <= b) {
-    posted_cache = __hip_atomic_load(&a.dev->posted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (posted_cache > b) break;
-    if (__hip_atomic_load(&a.dev->stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return 1;
-    if (b - posted_cache >= 2) {                 // >= 2 batches ahead: ~1 us naps
-      for (int k = 0; k < 4; ++k) __builtin_amdgcn_s_sleep(8);
-    } else {
-      for (unsigned k = 0; k < sleep_n; ++k) __builtin_amdgcn_s_sleep(1);
-      sleep_n = sleep_n < 8 ? sleep_n * 2 : 8;
-    }
-  }
-  persist_read_desc(a, b, sdesc);
-  return 0;
+// K7: the thread that read the descriptor of a micro-batch's item 0 stamps the batch's start.
+__device__ __forceinline__ void persist_stamp(const ccfd_persist_args& a, const ccfd_persist_desc& d,
+                                              unsigned long long it, int C) {
+  if (it % (unsigned long long)C == 0)
+    __hip_atomic_store(&a.dev->tstart[d.seq % (unsigned long long)a.ring], wall_clock64(), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Work item `it` (C items a micro-batch; `units` 16-row tiles or 64-row chunks an item, dealt
+// round-robin to the workgroup's waves) as wave `wave` sees it: the wave scores units u0,
+// u0 + #waves, ...  `stamp`: this thread stamps the micro-batch's start if the item is its
+// first (claimed items: item 0 is claimed first).
+struct PersistItem {
+  int slot, n, u0;
+  const unsigned char* xb;
+};
+
+__device__ __forceinline__ PersistItem persist_item(const ccfd_persist_args& a, const ccfd_persist_desc& d,
+                                                    unsigned long long it, int C, int units, int wave, bool stamp) {
+  if (stamp) persist_stamp(a, d, it, C);
+  return PersistItem{(int)(d.seq % (unsigned long long)a.ring), d.n, (int)(it % (unsigned long long)C) * units + wave,
+                     reinterpret_cast<const unsigned char*>(d.x)};
 }
 
 // Append this wave's fraud-routed rows (fr_lane; m = __ballot(fr_lane)) to the slot's
@@ -239,6 +257,65 @@ __device__ __forceinline__ void persist_item_done(const ccfd_persist_args& a, Ep
                                                   const ccfd_persist_desc& sdesc, int slot, int C, int tid) {
   persist_item_close(a, epi, sdesc, tid);
   if (tid == 0) persist_ticket(a, sdesc, slot, C);
+}
+
+// The static-item pipeline (persist_pipe_kernel, persist_gbdt_pipe_kernel): worker w (workgroup
+// 1 + w of W) takes items base + w, base + w + W, ... -- no claim atomic, the next item is known.
+// While item i is scored from one register buffer, the descriptor of item i + W is read and its
+// rows are issued into the other (when its micro-batch is posted), so one item's release and
+// ticket overlap the next item's PCIe round trip.  The kernel supplies
+//   issue(d, it, r): start the loads of this wave's share of item `it` into r;
+//   score(d, it, r): score it from r and end with persist_item_done (barriers, release, ticket).
+// `ra` / `rb` are only ever named statically (two stages, buffers swapped by name): an
+// in-flight load is never copied between registers, which would force an s_waitcnt vmcnt(0)
+// before the current item is scored.  s_pre (next item prefetched) and s_cmd (stop) are each
+// rewritten by thread 0 only after a barrier that every thread passes after reading the
+// previous value.  Returns when the host stops the kernel.
+template <class Regs, class Issue, class Score>
+__device__ __forceinline__ void persist_pipe_run(const ccfd_persist_args& a, int C, ccfd_persist_desc (&sdesc)[2],
+                                                 int& s_pre, int& s_cmd, Regs& ra, Regs& rb, Issue&& issue,
+                                                 Score&& score) {
+  const int tid = threadIdx.x;
+  const unsigned long long W = gridDim.x - 1;
+  unsigned long long item = __hip_atomic_load(&a.dev->work_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) +
+                            (unsigned long long)(blockIdx.x - 1);
+  unsigned long long posted_cache = 0;                   // thread 0 only
+  // one stage: score `it` from (dc, rc) while item it + W is fetched into (dn, rn); true = host stopped
+  auto stage = [&](ccfd_persist_desc& dc, Regs& rc, ccfd_persist_desc& dn, Regs& rn, unsigned long long it)
+      __attribute__((always_inline)) {
+    const unsigned long long nx = it + W;
+    if (tid == 0) {
+      s_pre = persist_try_item(a, C, posted_cache, nx, dn);
+      if (s_pre) persist_stamp(a, dn, nx, C);
+    }
+    __syncthreads();
+    const bool pre = s_pre != 0;
+    if (pre) issue(dn, nx, rn);                          // next item's rows in flight now
+    score(dc, it, rc);                                   // ends with barriers (persist_item_done)
+    if (!pre) {
+      if (tid == 0) {
+        s_cmd = persist_wait_item<true>(a, C, posted_cache, nx, dn);
+        if (!s_cmd) persist_stamp(a, dn, nx, C);
+      }
+      __syncthreads();
+      if (s_cmd) return true;
+      issue(dn, nx, rn);
+    }
+    return false;
+  };
+  if (tid == 0) {
+    s_cmd = persist_wait_item<true>(a, C, posted_cache, item, sdesc[0]);
+    if (!s_cmd) persist_stamp(a, sdesc[0], item, C);
+  }
+  __syncthreads();
+  if (s_cmd) return;
+  issue(sdesc[0], item, ra);
+  for (;;) {
+    if (stage(sdesc[0], ra, sdesc[1], rb, item)) break;
+    item += W;
+    if (stage(sdesc[1], rb, sdesc[0], ra, item)) break;
+    item += W;
+  }
 }
 
 }  // namespace ccfd

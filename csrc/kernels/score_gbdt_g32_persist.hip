@@ -65,7 +65,7 @@ __global__ __launch_bounds__(64 * kW) void persist_gbdt_g32_kernel(ccfd_persist_
 
   G32Wave w;                                              // this wave's share of the item (g32_item_commit)
   // transpose, lift, trees, row epilogue and flag list of one fetched 64-row chunk
-  auto score_chunk = [&](const ccfd_persist_desc& d, const G32Item& it, int chunk, G32Row& cur)
+  auto score_chunk = [&](const ccfd_persist_desc& d, const PersistItem& it, int chunk, G32Row& cur)
       __attribute__((always_inline)) {
     gx_rows<kG20>(xt[wave], lane, cur);
     unsigned b0[kF];
@@ -94,15 +94,7 @@ __global__ __launch_bounds__(64 * kW) void persist_gbdt_g32_kernel(ccfd_persist_
       t_claimed = wall_clock64();
       // persist_wait_item, split: the wait for the posting, then the descriptor read
       const unsigned long long b = it / (unsigned long long)C;
-      s_cmd = 0;
-      unsigned sleep_n = 1;
-      while (posted_cache <= b) {
-        posted_cache = __hip_atomic_load(&a.dev->posted, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (posted_cache > b) break;
-        if (__hip_atomic_load(&a.dev->stop, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) { s_cmd = 1; break; }
-        for (unsigned k = 0; k < sleep_n; ++k) __builtin_amdgcn_s_sleep(1);
-        sleep_n = sleep_n < 8 ? sleep_n * 2 : 8;
-      }
+      s_cmd = persist_wait_posted<false>(a, b, posted_cache);
       t_seen = wall_clock64();
       if (!s_cmd) persist_read_desc(a, b, sdesc);
       s_item = it;
@@ -114,8 +106,8 @@ __global__ __launch_bounds__(64 * kW) void persist_gbdt_g32_kernel(ccfd_persist_
     __syncthreads();
     if (s_cmd) break;
     const ccfd_persist_desc d = sdesc;                     // registers: no LDS wait in the epilogue
-    const G32Item it = g32_item(a, d, s_item, C, kW * cpw, wave, tid == 0);   // K7: item 0 is claimed first
-    const int n = it.n, c0 = it.c0;                       // this wave's chunks: c0 + kW*k
+    const PersistItem it = persist_item(a, d, s_item, C, kW * cpw, wave, tid == 0);   // K7: item 0 is claimed first
+    const int n = it.n, c0 = it.u0;                       // this wave's chunks: c0 + kW*k
     const unsigned char* xb = it.xb;
     // CCFD_G32_INFLIGHT=1: every chunk of the wave's share of the item in flight at once
     // (static registers: no copy of a pending load, so no vmcnt(0) between chunks)
@@ -202,29 +194,21 @@ __global__ __launch_bounds__(256) void persist_gbdt_pipe_kernel(ccfd_persist_arg
   const float* leaves = g32_leaves<D, false>(M, T, lv, tid, 256);
   epi_init(epi);
   __syncthreads();
-  const unsigned long long W = gridDim.x - 1;
-  unsigned long long item = __hip_atomic_load(&a.dev->work_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) +
-                            (unsigned long long)(blockIdx.x - 1);
-  unsigned long long posted_cache = 0;                    // thread 0 only
-
   G32Wave w;
-  // thread 0, as soon as it has read an item's descriptor: K7 stamp if the item starts a micro-batch
-  auto k7 = [&](const ccfd_persist_desc& d, unsigned long long it) __attribute__((always_inline)) {
-    g32_item(a, d, it, C, kG32Waves * CPW, wave, true);
-  };
   auto issue = [&](const ccfd_persist_desc& d, unsigned long long it, G32Row (&r)[CPW]) __attribute__((always_inline)) {
-    const G32Item i = g32_item(a, d, it, C, kG32Waves * CPW, wave, false);
+    const PersistItem i = persist_item(a, d, it, C, kG32Waves * CPW, wave, false);
 #pragma unroll
     for (int k = 0; k < CPW; ++k) {
-      const int chunk = i.c0 + kG32Waves * k;
+      const int chunk = i.u0 + kG32Waves * k;
       if (chunk * kG32Rows < i.n) gx_fetch<kG20>(i.xb, i.n, chunk, lane, r[k]);
     }
   };
-  auto score = [&](const ccfd_persist_desc& d, unsigned long long it, G32Row (&r)[CPW]) __attribute__((always_inline)) {
-    const G32Item i = g32_item(a, d, it, C, kG32Waves * CPW, wave, false);
+  auto score = [&](const ccfd_persist_desc& ds, unsigned long long it, G32Row (&r)[CPW]) __attribute__((always_inline)) {
+    const ccfd_persist_desc d = ds;                       // registers: no LDS reads in the epilogue
+    const PersistItem i = persist_item(a, d, it, C, kG32Waves * CPW, wave, false);
 #pragma unroll
     for (int k = 0; k < CPW; ++k) {
-      const int chunk = i.c0 + kG32Waves * k;
+      const int chunk = i.u0 + kG32Waves * k;
       if (chunk * kG32Rows >= i.n) break;                 // wave-uniform
       gx_rows<kG20>(xt[wave], lane, r[k]);
       unsigned b0[kF];
@@ -238,47 +222,9 @@ __global__ __launch_bounds__(256) void persist_gbdt_pipe_kernel(ccfd_persist_arg
     g32_item_commit(epi, w, a.counters[d.epoch & 1], lane);
     persist_item_done(a, epi, d, i.slot, C, tid);         // barriers, release, ticket
   };
-  // score `it` from (dc, rc) while item it + W is fetched into (dn, rn); true = host stopped
-  auto stage = [&](ccfd_persist_desc& dc, G32Row (&rc)[CPW], ccfd_persist_desc& dn, G32Row (&rn)[CPW],
-                   unsigned long long it) __attribute__((always_inline)) {
-    const unsigned long long nx = it + W;
-    if (tid == 0) {
-      s_pre = persist_try_item(a, C, posted_cache, nx, dn);
-      if (s_pre) k7(dn, nx);
-    }
-    __syncthreads();
-    const bool pre = s_pre != 0;
-    const ccfd_persist_desc d = dc;                       // registers: no LDS reads in the epilogue
-    if (pre) issue(dn, nx, rn);                           // next item's rows in flight now
-    score(d, it, rc);                                     // ends with barriers (persist_item_done)
-    if (!pre) {
-      if (tid == 0) {
-        s_cmd = persist_wait_far(a, C, posted_cache, nx, dn);
-        if (!s_cmd) k7(dn, nx);
-      }
-      __syncthreads();
-      if (s_cmd) return true;
-      issue(dn, nx, rn);
-    }
-    return false;
-  };
-
-  if (tid == 0) {
-    s_cmd = persist_wait_far(a, C, posted_cache, item, sdesc[0]);
-    if (!s_cmd) k7(sdesc[0], item);
-  }
-  __syncthreads();
-  if (s_cmd) return;
   G32Row ra[CPW], rb[CPW];
-  issue(sdesc[0], item, ra);
-  for (;;) {
-    if (stage(sdesc[0], ra, sdesc[1], rb, item)) break;
-    item += W;
-    if (stage(sdesc[1], rb, sdesc[0], ra, item)) break;
-    item += W;
-  }
+  persist_pipe_run(a, C, sdesc, s_pre, s_cmd, ra, rb, issue, score);
 }
-
 
 template <int D, bool kG20>
 static int launch_persist_g32_f(const ccfd_persist_args& a0, int grid, hipStream_t s) {
@@ -290,26 +236,24 @@ static int launch_persist_g32_f(const ccfd_persist_args& a0, int grid, hipStream
   if (g32_env("CCFD_G32_INFLIGHT", 0, 0, 1) == 0) a.flags |= CCFD_ARG_CHUNK_RING;
   const bool gl = ((long)a.gbdt_trees << D) > kG32LeafLds || g32_env("CCFD_G32_GLOBAL_LEAVES", 0, 0, 1);
   const size_t lds = gl ? 0 : (size_t)a.gbdt_trees * (1 << D) * sizeof(float);
-  if (a.flags & CCFD_ARG_PIPE_ITEMS) {                    // pipelined static 512-row items
-    if (gl || a.tiles_per_wave != 2 || grid < 2) return -2;
-    if (a.rules) hipLaunchKernelGGL((persist_gbdt_pipe_kernel<D, true, kG20, 2>), dim3(grid), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((persist_gbdt_pipe_kernel<D, false, kG20, 2>), dim3(grid), dim3(256), lds, s, a);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
-  }
+  const bool pipe = (a.flags & CCFD_ARG_PIPE_ITEMS) != 0;   // pipelined static 512-row items
+  if (pipe && (gl || a.tiles_per_wave != 2 || grid < 2)) return -2;
+  dispatch_bool(a.rules != nullptr, [&](auto kr) {
+    constexpr bool kR = decltype(kr)::value;
+    if (pipe) {
+      hipLaunchKernelGGL((persist_gbdt_pipe_kernel<D, kR, kG20, 2>), dim3(grid), dim3(256), lds, s, a);
+      return;
+    }
 #ifdef CCFD_EXP_G20_WAVES8
-  if (!gl && a.tiles_per_wave % 2 == 0) {
-    if (a.rules) hipLaunchKernelGGL((persist_gbdt_g32_kernel<D, true, false, kG20, 8>), dim3(grid), dim3(512), lds, s, a);
-    else hipLaunchKernelGGL((persist_gbdt_g32_kernel<D, false, false, kG20, 8>), dim3(grid), dim3(512), lds, s, a);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
-  }
+    if (!gl && a.tiles_per_wave % 2 == 0) {
+      hipLaunchKernelGGL((persist_gbdt_g32_kernel<D, kR, false, kG20, 8>), dim3(grid), dim3(512), lds, s, a);
+      return;
+    }
 #endif
-  if (gl) {
-    if (a.rules) hipLaunchKernelGGL((persist_gbdt_g32_kernel<D, true, true, kG20>), dim3(grid), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((persist_gbdt_g32_kernel<D, false, true, kG20>), dim3(grid), dim3(256), 0, s, a);
-  } else {
-    if (a.rules) hipLaunchKernelGGL((persist_gbdt_g32_kernel<D, true, false, kG20>), dim3(grid), dim3(256), lds, s, a);
-    else hipLaunchKernelGGL((persist_gbdt_g32_kernel<D, false, false, kG20>), dim3(grid), dim3(256), lds, s, a);
-  }
+    dispatch_bool(gl, [&](auto kgl) {                     // lds == 0 with global leaves
+      hipLaunchKernelGGL((persist_gbdt_g32_kernel<D, kR, decltype(kgl)::value, kG20>), dim3(grid), dim3(256), lds, s, a);
+    });
+  });
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
@@ -341,8 +285,9 @@ int item_trace_dump(const char* path) {
 int launch_persist_gbdt_g32(const ccfd_persist_args& a, int grid, hipStream_t s) {
   if (a.gbdt_trees <= 0 || a.gbdt_depth < 1 || a.gbdt_depth > 8) return -2;
   return dispatch_depth(a.gbdt_depth, [&](auto d) {
-    return (a.flags & CCFD_ARG_WIRE_G20) ? launch_persist_g32_f<decltype(d)::value, true>(a, grid, s)
-                                         : launch_persist_g32_f<decltype(d)::value, false>(a, grid, s);
+    return dispatch_bool((a.flags & CCFD_ARG_WIRE_G20) != 0, [&](auto g20) {
+      return launch_persist_g32_f<decltype(d)::value, decltype(g20)::value>(a, grid, s);
+    });
   });
 }
 

@@ -170,15 +170,15 @@ __global__ __launch_bounds__(256) void persist_gbdt_shadow_kernel(ccfd_persist_s
     __syncthreads();
     if (s_cmd) break;
     const ccfd_persist_desc d = sdesc;                     // registers: no LDS wait in the epilogue
-    const G32Item it = g32_item(a, d, s_item, C, kG32Waves * cpw, wave, tid == 0);   // K7: item 0 is claimed first
+    const PersistItem it = persist_item(a, d, s_item, C, kG32Waves * cpw, wave, tid == 0);   // K7: item 0 is claimed first
     const int n = it.n;
 
     ShadowWave s;                                          // this wave's share of the item
     G32Row pre;
-    if (it.c0 * kG32Rows < n) gx_fetch<kG20>(it.xb, n, it.c0, lane, pre);
+    if (it.u0 * kG32Rows < n) gx_fetch<kG20>(it.xb, n, it.u0, lane, pre);
 #pragma unroll 1
     for (int k = 0; k < cpw; ++k) {
-      const int chunk = it.c0 + kG32Waves * k;             // this wave's chunks: c0 + 4k
+      const int chunk = it.u0 + kG32Waves * k;             // this wave's chunks: u0 + 4k
       if (chunk * kG32Rows >= n) break;                    // wave-uniform
       G32Row cur = pre;
       if (k + 1 < cpw && (chunk + kG32Waves) * kG32Rows < n) gx_fetch<kG20>(it.xb, n, chunk + kG32Waves, lane, pre);

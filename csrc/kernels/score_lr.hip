@@ -7,6 +7,8 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "lr_core.h"
+#include "tile_core.h"
 #include "wire_body.h"
 
 namespace ccfd {
@@ -36,20 +38,10 @@ __device__ __forceinline__ void lr_body(const ccfd_score_args& a, int blk, int n
   }
   epi_init(epi);
 
-  const char* blob = reinterpret_cast<const char*>(a.blob);
-  const unsigned flags = *reinterpret_cast<const unsigned*>(blob + 4);
-  const float b = *reinterpret_cast<const float*>(blob + 8);
-  const float* mu = reinterpret_cast<const float*>(blob + 64) + 8 * g;
-  const float* isg = reinterpret_cast<const float*>(blob + 192) + 8 * g;
-  const float* w = reinterpret_cast<const float*>(blob + 320) + 8 * g;
-  float wm[8], ws[8], wmu[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) { wmu[j] = mu[j]; ws[j] = isg[j]; wm[j] = w[j]; }
-  const bool log_amount = (flags & 1u) != 0;
+  const LrLane L = lr_lane(reinterpret_cast<const char*>(a.blob), g);
   __syncthreads();
 
-  unsigned fraud = 0, rows = 0;
-  unsigned long long psum = 0;
+  TileWave w;
   float* tile_lds = sx[kContig ? wave : 0];
   for (; tile < ntiles; tile += tstride) {
     const int row = tile * kTileRows + c;
@@ -68,39 +60,18 @@ __device__ __forceinline__ void lr_body(const ccfd_score_args& a, int blk, int n
       for (int j = 0; j < 8; ++j) xv[j] = (valid && (8 * g + j) < kF) ? xr[j] : 0.f;
     }
     const float amount = xv[5];
-    if (g == 3) {
-      xv[6] = 0.f; xv[7] = 0.f;
-      if (log_amount) xv[5] = log1pf(fmaxf(xv[5], 0.f));
-    }
-    float z = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) z = fmaf((xv[j] - wmu[j]) * ws[j], wm[j], z);
-    z += __shfl_xor(z, 16);
-    z += __shfl_xor(z, 32);
-    const float p = sigmoid(z + b);
-    bool fr;
+    const float p = lr_proba(L, xv, g);
+    bool rf;
     if constexpr (kR) {                                 // configurable routing rules (rules.h)
-      if (g == 3) xv[5] = amount;
-      fr = valid && rule_route(a.rules, __shfl(p, c), [&](int j) { return lane_feature<false>(xv, j, c); });
+      if (g == 3) xv[5] = amount;                       // lr_proba replaced Amount by its log1p
+      rf = valid && rule_route(a.rules, __shfl(p, c), [&](int j) { return lane_feature<false>(xv, j, c); });
     } else {
-      fr = valid && (p >= a.threshold);
+      rf = p >= a.threshold;
     }
-    if (valid && g == 0) {
-      if (a.proba) st_g(a.proba + row, p);
-      if (a.route) st_g(a.route + row, (uint8_t)(fr ? 1 : 0));
-      psum += (unsigned)(p * 1e6f + 0.5f);
-    }
-    fraud += __popcll(__ballot(fr && g == 0));
-    rows += __popcll(__ballot(valid && g == 0));
-    if (valid && g == 3) atomicAdd(&epi.hist[(fr ? kNB : 0) + amount_bucket_fast(amount)], 1u);
-    emit_flagged(a, fr && g == 0, row);
+    const TileRowOut o = tile_row_epilogue(epi, w, p, rf, amount, row, a.n, g, a.proba, a.route);
+    emit_flagged(a, o.fr && g == 0, row);
   }
-  psum = wave_sum_u64(psum);
-  if (lane == 0) {
-    atomicAdd(&epi.fraud, fraud);
-    atomicAdd(&epi.rows, rows);
-    atomicAdd(&epi.psum_e6, psum);
-  }
+  tile_wave_commit(epi, w, lane);
   epi_flush(epi, a.counters);
   signal_done(a, (unsigned)nblk);
 }

@@ -21,6 +21,7 @@
 
 #include "mlp_core.h"
 #include "rules.h"
+#include "tile_core.h"
 #include "wire_body.h"
 
 namespace ccfd {
@@ -66,8 +67,7 @@ __device__ __forceinline__ void mlp_body(const ccfd_score_args& a, int blk, int 
 
   const MlpLane L = mlp_lane(W, g);
   const float thr = a.threshold;
-  unsigned fraud = 0, rows = 0;
-  unsigned long long psum = 0;
+  TileWave w;
   float* tile_lds = sx[wave];
 
   for (; tile < ntiles; tile += tstride) {
@@ -93,30 +93,17 @@ __device__ __forceinline__ void mlp_body(const ccfd_score_args& a, int blk, int 
     }
     float amount;
     const float p = mlp_tile(W, L, xv, g, lane, amount);
-    bool fr;
+    bool rf;
     if constexpr (kR) {                                 // configurable routing rules (rules.h)
       if (g == 3) xv[5] = amount;                       // mlp_tile replaced Amount by its log1p
-      fr = valid && rule_route(a.rules, __shfl(p, c), [&](int j) { return lane_feature<false>(xv, j, c); });
+      rf = valid && rule_route(a.rules, __shfl(p, c), [&](int j) { return lane_feature<false>(xv, j, c); });
     } else {
-      fr = valid && (p >= thr);
+      rf = p >= thr;
     }
-
-    if (valid && g == 0) {
-      if (a.proba) st_g(a.proba + row, p);
-      if (a.route) st_g(a.route + row, (uint8_t)(fr ? 1 : 0));
-      psum += (unsigned)(p * 1e6f + 0.5f);              // p in [0,1]: u32 convert, u64 sum
-    }
-    fraud += __popcll(__ballot(fr && g == 0));
-    rows += __popcll(__ballot(valid && g == 0));
-    if (valid && g == 3) atomicAdd(&epi.hist[(fr ? kNB : 0) + amount_bucket_fast(amount)], 1u);
-    emit_flagged(a, fr && g == 0, row);
+    const TileRowOut o = tile_row_epilogue(epi, w, p, rf, amount, row, a.n, g, a.proba, a.route);
+    emit_flagged(a, o.fr && g == 0, row);
   }
-  psum = wave_sum_u64(psum);
-  if (lane == 0) {
-    atomicAdd(&epi.fraud, fraud);
-    atomicAdd(&epi.rows, rows);
-    atomicAdd(&epi.psum_e6, psum);
-  }
+  tile_wave_commit(epi, w, lane);
   epi_flush(epi, a.counters);
   signal_done(a, (unsigned)nblk);
 }

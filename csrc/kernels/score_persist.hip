@@ -13,7 +13,7 @@
 //   at once and score them in pairs, other sizes prefetch the next tile while the current
 //   one computes (f32 rows via a wave-private LDS tile); the same fused math as the
 //   per-batch kernels (mlp_core.h), outputs written straight to host-mapped memory,
-//   fraud rows appended to the descriptor's compacted flag list
+//   fraud rows appended to the descriptor's compacted flag list (row epilogue: tile_core.h)
 //   counters + amount histogram -> counters[desc.epoch] (one atomic set per item)
 //   release (system scope) + ticket on remaining[b % R]; the last ticket publishes
 //   ctl->done[b % R] = {b + 1, #flagged, t_start, t_end}
@@ -24,9 +24,11 @@
 // (remaining/nflag reset by the last ticket) safe to reuse.
 #include <type_traits>
 
+#include "lr_core.h"
 #include "mlp_core.h"
 #include "persist_core.h"
 #include "rules.h"
+#include "tile_core.h"
 
 namespace ccfd {
 
@@ -50,27 +52,21 @@ __global__ __launch_bounds__(256) void persist_kernel(ccfd_persist_args a) {
 
   if (kModel == CCFD_MODEL_MLP)
     mlp_stage(a.blob, sblob, tid, 256, (a.flags & CCFD_ARG_WIRE_W64) ? kMlpBlobWire : kMlpBlob);
-  else for (int i = tid; i < 448 / 16; i += 256) reinterpret_cast<int4*>(sblob)[i] = reinterpret_cast<const int4*>(a.blob)[i];
+  else for (int i = tid; i < kLrBlob / 16; i += 256) reinterpret_cast<int4*>(sblob)[i] = reinterpret_cast<const int4*>(a.blob)[i];
   epi_init(epi);
   __syncthreads();
 
   MlpLane L{};
   MlpWireLane LW{};
-  float wm[8];
+  LrLane LL{};
   if (kModel == CCFD_MODEL_MLP) {
     L = mlp_lane(sblob, g);
     LW = mlp_wire_lane(sblob);
   } else {
-    const unsigned flags = *reinterpret_cast<const unsigned*>(sblob + 4);
-    L.b3 = *reinterpret_cast<const float*>(sblob + 8);
-    L.log_amount = (flags & 1u) != 0;
-    const float* mu = reinterpret_cast<const float*>(sblob + 64) + 8 * g;
-    const float* isg = reinterpret_cast<const float*>(sblob + 192) + 8 * g;
-    const float* w = reinterpret_cast<const float*>(sblob + 320) + 8 * g;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) { L.mu[j] = mu[j]; L.isg[j] = isg[j]; wm[j] = w[j]; }
+    LL = lr_lane(sblob, g);
   }
   float* tile_lds = sx[wave];
+  TileWave w;                              // this wave's share of the item (tile_item_commit)
   unsigned long long posted_cache = 0;     // thread 0 only
 
   // Workgroup 0 is the DOORBELL (persist_core.h): its first wave alone polls host memory.
@@ -84,55 +80,29 @@ __global__ __launch_bounds__(256) void persist_kernel(ccfd_persist_args a) {
     __syncthreads();
     if (s_cmd) break;
 
-    const unsigned long long item = s_item;
     // the item's descriptor in registers: the epilogue reads its pointers with no LDS wait
     const ccfd_persist_desc dsc = sdesc;
-    const int chunk = (int)(item % (unsigned long long)C);
-    const int slot = (int)(dsc.seq % (unsigned long long)a.ring);
-    const int n = dsc.n;
-    const float* x = dsc.x;
     const int kTilesPerWave = a.tiles_per_wave;
-    const int tile0 = chunk * (4 * kTilesPerWave) + wave;      // wave w: tiles tile0 + 4k
-    if (chunk == 0 && tid == 0)                                // K7: micro-batch start (item 0 claimed first)
-      __hip_atomic_store(&a.dev->tstart[slot], wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const PersistItem it = persist_item(a, dsc, s_item, C, 4 * kTilesPerWave, wave, tid == 0);   // K7: item 0 is claimed first
+    const int slot = it.slot, n = it.n, tile0 = it.u0;         // wave w: tiles tile0 + 4k
+    const float* x = dsc.x;
     auto avail = [&](int t) { return min(kTileRows, n - t * kTileRows) * kF * 4; };
     const bool wire = (a.flags & CCFD_ARG_WIRE_W64) != 0;       // uniform per launch
-    const unsigned char* xw = reinterpret_cast<const unsigned char*>(x);
-    unsigned nf_w = 0, nv_w = 0;
-    unsigned long long ps_w = 0;
-    // LR on one lane group's 8 features (the g == 3 group also carries Time / Amount)
-    auto lr_p = [&](float (&xv)[8]) __attribute__((always_inline)) {
-      if (g == 3) { xv[6] = 0.f; xv[7] = 0.f; if (L.log_amount) xv[5] = log1pf(fmaxf(xv[5], 0.f)); }
-      float z = 0.f;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) z = fmaf((xv[j] - L.mu[j]) * L.isg[j], wm[j], z);
-      z += __shfl_xor(z, 16);
-      z += __shfl_xor(z, 32);
-      return sigmoid(z + L.b3);
-    };
-    // per-tile epilogue: outputs, route, counters, amount histogram, compacted fraud list;
-    // xr = the tile's raw features (routing rules only)
+    const unsigned char* xw = it.xb;
+    // per-tile epilogue (tile_core.h) and the compacted fraud list; xr = the tile's raw
+    // features (routing rules only)
     auto finish = [&](float p, float amount, int tile, float (&xr)[8]) __attribute__((always_inline)) {
       const int row = tile * kTileRows + c;
-      const bool valid = row < n;
-      bool fr;
+      bool rf;
       if constexpr (kR) {                               // configurable routing rules (rules.h)
         const float pr = __shfl(p, c);
-        fr = valid && (wire ? rule_route(a.rules, pr, [&](int j) { return lane_feature<true>(xr, j, c); })
-                            : rule_route(a.rules, pr, [&](int j) { return lane_feature<false>(xr, j, c); }));
+        rf = row < n && (wire ? rule_route(a.rules, pr, [&](int j) { return lane_feature<true>(xr, j, c); })
+                              : rule_route(a.rules, pr, [&](int j) { return lane_feature<false>(xr, j, c); }));
       } else {
-        fr = valid && (p >= a.threshold);
+        rf = p >= a.threshold;
       }
-      if (valid && g == 0) {
-        if (dsc.proba) st_g(dsc.proba + row, p);
-        if (dsc.route) st_g(dsc.route + row, (uint8_t)(fr ? 1 : 0));
-        ps_w += (unsigned long long)(p * 1e6f + 0.5f);
-      }
-      const unsigned long long m = __ballot(fr && g == 0);
-      nf_w += __popcll(m);
-      nv_w += __popcll(__ballot(valid && g == 0));
-      if (valid && g == 3) atomicAdd(&epi.hist[(fr ? kNB : 0) + amount_bucket(amount)], 1u);
-      persist_emit_flagged(a, dsc, slot, m, fr && g == 0, row, lane);
+      const TileRowOut o = tile_row_epilogue(epi, w, p, rf, amount, row, n, g, dsc.proba, dsc.route);
+      persist_emit_flagged(a, dsc, slot, o.m, o.fr && g == 0, row, lane);
     };
     // W64 items of 2, 4 or 8 tiles per wave (128 / 256 / 512 rows): every tile
     // of the item in flight at once -- the item costs one PCIe round trip instead of one per
@@ -158,8 +128,8 @@ __global__ __launch_bounds__(256) void persist_kernel(ccfd_persist_args a) {
           float la[8], lb[8];
 #pragma unroll
           for (int j = 0; j < 8; ++j) { la[j] = xa[j]; lb[j] = xb[j]; }
-          pa = lr_p(la);
-          pb = lr_p(lb);
+          pa = lr_proba(LL, la, g);
+          pb = lr_proba(LL, lb, g);
         }
         finish(pa, __uint_as_float(r[k].v.w), ta, xa);
         finish(pb, __uint_as_float(r[k + 1].v.w), ta + 4, xb);   // rows >= n: no-op epilogue
@@ -213,22 +183,18 @@ __global__ __launch_bounds__(256) void persist_kernel(ccfd_persist_args a) {
           }
         } else {
           amount = xv[5];
-          p = lr_p(xv);
+          p = lr_proba(LL, xv, g);
         }
         finish(p, amount, tile, xr);
       }
     }
-    ps_w = wave_sum_u64(ps_w);
-    if (lane == 0 && nv_w) {
-      atomicAdd(&epi.fraud, nf_w);
-      atomicAdd(&epi.rows, nv_w);
-      atomicAdd(&epi.psum_e6, ps_w);
-    }
+    tile_item_commit(epi, w, lane);
     persist_item_done(a, epi, dsc, slot, C, tid);
   }
 }
 
-// Pipelined static work items (CCFD_ARG_PIPE_ITEMS; MLP on W64 rows).  A CU reading host
+// Pipelined static work items (CCFD_ARG_PIPE_ITEMS; MLP on W64 rows; the pipeline itself is
+// persist_pipe_run, persist_core.h).  A CU reading host
 // memory sustains only ~2 GB/s (a few KB of requests outstanding over a ~2 us PCIe round
 // trip), so a micro-batch finishes soonest when its 256 KB is spread over many CUs: small
 // items (64 / 128 rows, one per workgroup).  The claim-score-release chain of one item is
@@ -250,9 +216,7 @@ __global__ __launch_bounds__(256) void persist_pipe_kernel(ccfd_persist_args a) 
   __shared__ __attribute__((aligned(16))) char sblob[kMlpBlobWire];
   __shared__ EpilogueLds epi;
   __shared__ ccfd_persist_desc sdesc[2];
-  // two flags: s_pre (next item prefetched) and s_cmd (stop) are each rewritten by thread 0
-  // only after a barrier that every thread passes after reading the previous value
-  __shared__ int s_pre, s_cmd;
+  __shared__ int s_pre, s_cmd;                           // rewritten by thread 0 after a barrier only
 
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
@@ -266,54 +230,29 @@ __global__ __launch_bounds__(256) void persist_pipe_kernel(ccfd_persist_args a) 
     return;
   }
   const MlpWireLane LW = mlp_wire_lane(sblob);
-  const unsigned long long W = gridDim.x - 1;
-  unsigned long long item = __hip_atomic_load(&a.dev->work_next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) +
-                            (unsigned long long)(blockIdx.x - 1);
-  unsigned long long posted_cache = 0;                   // thread 0 only
+  TileWave w;
 
-  auto stamp = [&](const ccfd_persist_desc& d, unsigned long long it) __attribute__((always_inline)) {
-    if (it % (unsigned long long)C == 0)                // K7: micro-batch start
-      __hip_atomic_store(&a.dev->tstart[d.seq % (unsigned long long)a.ring], wall_clock64(), __ATOMIC_RELAXED,
-                         __HIP_MEMORY_SCOPE_AGENT);
-  };
   auto issue = [&](const ccfd_persist_desc& d, unsigned long long it, WireRegs (&r)[T]) __attribute__((always_inline)) {
-    const int tile0 = (int)(it % (unsigned long long)C) * (4 * T) + wave;   // wave w: tiles tile0 + 4k
-    const unsigned char* xw = reinterpret_cast<const unsigned char*>(d.x);
+    const PersistItem i = persist_item(a, d, it, C, 4 * T, wave, false);   // wave w: tiles u0 + 4k
 #pragma unroll
-    for (int k = 0; k < T; ++k) wire_issue(xw, d.n, tile0 + 4 * k, c, g, r[k]);
+    for (int k = 0; k < T; ++k) wire_issue(i.xb, i.n, i.u0 + 4 * k, c, g, r[k]);
   };
   // score item `it` (rows in r), counters into LDS, outputs to the host, then release + ticket
-  auto score = [&](const ccfd_persist_desc& d, unsigned long long it, const WireRegs (&r_in)[T]) __attribute__((always_inline)) {
-    const int slot = (int)(d.seq % (unsigned long long)a.ring);
-    const int n = d.n;
-    const int tile0 = (int)(it % (unsigned long long)C) * (4 * T) + wave;
-    WireRegs r[T];
-#pragma unroll
-    for (int k = 0; k < T; ++k) r[k] = r_in[k];
-    unsigned nf_w = 0, nv_w = 0;
-    unsigned long long ps_w = 0;
+  auto score = [&](const ccfd_persist_desc& d, unsigned long long it, WireRegs (&r)[T]) __attribute__((always_inline)) {
+    const PersistItem i = persist_item(a, d, it, C, 4 * T, wave, false);
+    const int n = i.n, tile0 = i.u0;
     auto finish = [&](float p, const WireRegs& rr, int tile) __attribute__((always_inline)) {
       const int row = tile * kTileRows + c;
-      const bool valid = row < n;
-      bool fr;
+      bool rf;
       if constexpr (kR) {
         float xr[8];
         wire_features(rr, g, xr);
-        fr = valid && rule_route(a.rules, __shfl(p, c), [&](int j) { return lane_feature<true>(xr, j, c); });
+        rf = row < n && rule_route(a.rules, __shfl(p, c), [&](int j) { return lane_feature<true>(xr, j, c); });
       } else {
-        fr = valid && (p >= a.threshold);
+        rf = p >= a.threshold;
       }
-      if (valid && g == 0) {
-        if (d.proba) st_g(d.proba + row, p);
-        if (d.route) st_g(d.route + row, (uint8_t)(fr ? 1 : 0));
-        ps_w += (unsigned long long)(p * 1e6f + 0.5f);
-      }
-      const unsigned long long m = __ballot(fr && g == 0);
-      nf_w += __popcll(m);
-      nv_w += __popcll(__ballot(valid && g == 0));
-      const float amount = __uint_as_float(rr.v.w);
-      if (valid && g == 3) atomicAdd(&epi.hist[(fr ? kNB : 0) + amount_bucket_fast(amount)], 1u);
-      persist_emit_flagged(a, d, slot, m, fr && g == 0, row, lane);
+      const TileRowOut o = tile_row_epilogue(epi, w, p, rf, __uint_as_float(rr.v.w), row, n, g, d.proba, d.route);
+      persist_emit_flagged(a, d, i.slot, o.m, o.fr && g == 0, row, lane);
     };
     if (tile0 * kTileRows < n) {
       if constexpr (T == 2) {
@@ -325,53 +264,11 @@ __global__ __launch_bounds__(256) void persist_pipe_kernel(ccfd_persist_args a) 
         finish(mlp_tile_w64(sblob, LW, r[0], g, lane), r[0], tile0);
       }
     }
-    ps_w = wave_sum_u64(ps_w);
-    if (lane == 0 && nv_w) {
-      atomicAdd(&epi.fraud, nf_w);
-      atomicAdd(&epi.rows, nv_w);
-      atomicAdd(&epi.psum_e6, ps_w);
-    }
-    persist_item_done(a, epi, d, slot, C, tid);
+    tile_item_commit(epi, w, lane);
+    persist_item_done(a, epi, d, i.slot, C, tid);
   };
-  // one pipeline stage: score `it` from (dc, rc) while item it + W is fetched into (dn, rn);
-  // returns true when the host stopped the kernel
-  auto stage = [&](ccfd_persist_desc& dc, const WireRegs (&rc)[T], ccfd_persist_desc& dn, WireRegs (&rn)[T],
-                   unsigned long long it) __attribute__((always_inline)) {
-    const unsigned long long nx = it + W;
-    if (tid == 0) {
-      s_pre = persist_try_item(a, C, posted_cache, nx, dn);
-      if (s_pre) stamp(dn, nx);
-    }
-    __syncthreads();
-    const bool pre = s_pre != 0;
-    if (pre) issue(dn, nx, rn);                          // next item's rows in flight now
-    score(dc, it, rc);                                   // ends with barriers (persist_item_done)
-    if (!pre) {
-      if (tid == 0) {
-        s_cmd = persist_wait_far(a, C, posted_cache, nx, dn);
-        if (!s_cmd) stamp(dn, nx);
-      }
-      __syncthreads();
-      if (s_cmd) return true;
-      issue(dn, nx, rn);
-    }
-    return false;
-  };
-
-  if (tid == 0) {
-    s_cmd = persist_wait_far(a, C, posted_cache, item, sdesc[0]);
-    if (!s_cmd) stamp(sdesc[0], item);
-  }
-  __syncthreads();
-  if (s_cmd) return;
   WireRegs ra[T], rb[T];
-  issue(sdesc[0], item, ra);
-  for (;;) {
-    if (stage(sdesc[0], ra, sdesc[1], rb, item)) break;
-    item += W;
-    if (stage(sdesc[1], rb, sdesc[0], ra, item)) break;
-    item += W;
-  }
+  persist_pipe_run(a, C, sdesc, s_pre, s_cmd, ra, rb, issue, score);
 }
 
 }  // namespace
@@ -383,27 +280,18 @@ extern "C" int ccfd_persist_launch(const ccfd_persist_args* a, int grid, void* s
   if (!a || !a->ctl || !a->desc || !a->dev || !a->blob) return -1;
   if (a->ring <= 0 || a->ring > CCFD_PERSIST_MAX_RING || a->items_per_batch <= 0 || a->tiles_per_wave <= 0) return -2;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  const bool pipe = a->model == CCFD_MODEL_MLP && (a->flags & CCFD_ARG_PIPE_ITEMS);
+  if (pipe && (!(a->flags & CCFD_ARG_WIRE_W64) || grid < 2 || a->tiles_per_wave < 1 || a->tiles_per_wave > 2)) return -2;
+  if (a->model == CCFD_MODEL_GBDT && (a->flags & CCFD_ARG_WIRE_G32)) return launch_persist_gbdt_g32(*a, grid, s);
+  if (a->model != CCFD_MODEL_MLP && a->model != CCFD_MODEL_LR) return -3;
   // routing rules: separate instantiations, so threshold-only kernels keep their registers
-  if (a->model == CCFD_MODEL_MLP && (a->flags & CCFD_ARG_PIPE_ITEMS)) {
-    if (!(a->flags & CCFD_ARG_WIRE_W64) || grid < 2) return -2;
-    const bool r = a->rules != nullptr;
-    switch (a->tiles_per_wave) {
-      case 1: if (r) hipLaunchKernelGGL((persist_pipe_kernel<true, 1>), dim3(grid), dim3(256), 0, s, *a);
-              else hipLaunchKernelGGL((persist_pipe_kernel<false, 1>), dim3(grid), dim3(256), 0, s, *a); break;
-      case 2: if (r) hipLaunchKernelGGL((persist_pipe_kernel<true, 2>), dim3(grid), dim3(256), 0, s, *a);
-              else hipLaunchKernelGGL((persist_pipe_kernel<false, 2>), dim3(grid), dim3(256), 0, s, *a); break;
-      default: return -2;
-    }
-  } else if (a->model == CCFD_MODEL_MLP) {
-    if (a->rules) hipLaunchKernelGGL((persist_kernel<CCFD_MODEL_MLP, true>), dim3(grid), dim3(256), 0, s, *a);
-    else hipLaunchKernelGGL((persist_kernel<CCFD_MODEL_MLP, false>), dim3(grid), dim3(256), 0, s, *a);
-  } else if (a->model == CCFD_MODEL_LR) {
-    if (a->rules) hipLaunchKernelGGL((persist_kernel<CCFD_MODEL_LR, true>), dim3(grid), dim3(256), 0, s, *a);
-    else hipLaunchKernelGGL((persist_kernel<CCFD_MODEL_LR, false>), dim3(grid), dim3(256), 0, s, *a);
-  } else if (a->model == CCFD_MODEL_GBDT && (a->flags & CCFD_ARG_WIRE_G32)) {
-    return launch_persist_gbdt_g32(*a, grid, s);
-  } else {
-    return -3;
-  }
+  dispatch_bool(a->rules != nullptr, [&](auto kr) {
+    constexpr bool kR = decltype(kr)::value;
+    const dim3 g(grid), b(256);
+    if (pipe && a->tiles_per_wave == 1) hipLaunchKernelGGL((persist_pipe_kernel<kR, 1>), g, b, 0, s, *a);
+    else if (pipe) hipLaunchKernelGGL((persist_pipe_kernel<kR, 2>), g, b, 0, s, *a);
+    else if (a->model == CCFD_MODEL_MLP) hipLaunchKernelGGL((persist_kernel<CCFD_MODEL_MLP, kR>), g, b, 0, s, *a);
+    else hipLaunchKernelGGL((persist_kernel<CCFD_MODEL_LR, kR>), g, b, 0, s, *a);
+  });
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }

@@ -11,8 +11,9 @@
 // the shadow carry the same bits as rows scored with B as the champion.
 //
 //   * score_shadow_kernel: one launch per micro-batch (plain launches, score_sync, the engine's
-//     exec_mode launch).  Champion epilogue as in wire_body.h (outputs, route, counters, amount
-//     histogram, staged flag list, completion record).
+//     exec_mode launch).  Champion epilogue as in wire_body.h (tile_row_epilogue_lanes of
+//     tile_core.h: outputs, route, counters, amount histogram; staged flag list, completion
+//     record).
 //   * persist_shadow_kernel: the claimed-item path of score_persist.hip for W64 items of 2, 4
 //     or 8 tiles per wave, protocol helpers of persist_core.h unchanged: a workgroup waits only
 //     for the host and leaves on `stop`; workgroup 0 is the doorbell.
@@ -29,6 +30,7 @@
 #include "mlp_core.h"
 #include "persist_core.h"
 #include "shadow_core.h"
+#include "tile_core.h"
 
 namespace ccfd {
 
@@ -87,35 +89,23 @@ __global__ __launch_bounds__(64 * kShadowWaves) void score_shadow_kernel(ccfd_sh
 
   const float thr = a.threshold;
   FlagStage fls{flbuf[wave], 0u};
-  unsigned fraud = 0, rows = 0;
-  unsigned long long psum = 0;
+  TileWave w;
   ShadowAcc sw;
   HistLanes hl;
   hist_lanes_init(hl, g);
-  // p: champion, q: challenger proba_1 of row c of tile t (identical in the 4 lane groups)
+  // p: champion, q: challenger proba_1 of row c of tile t (identical in the 4 lane groups):
+  // the champion's epilogue, then the challenger's output and counts
   auto finish = [&](float p, float q, float amount, int t) __attribute__((always_inline)) {
     const int row = t * kTileRows + c;
-    const bool valid = row < n;
-    const bool fr = valid && (p >= thr);
-    const bool sf = valid && (q >= thr);
-    if (valid && g == 0) {
-      if (a.proba) st_g(a.proba + row, p);
-      if (a.route) st_g(a.route + row, (uint8_t)(fr ? 1 : 0));
-      psum += (unsigned)(p * 1e6f + 0.5f);
+    const TileRowOut o = tile_row_epilogue_lanes(epi, w, hl, p, p >= thr, amount, t, n, g, c, a.proba, a.route);
+    const bool sf = o.valid && (q >= thr);
+    if (o.valid && g == 0) {
       if (sa.shadow_proba) st_g(sa.shadow_proba + row, q);
       shadow_row(sw, p, q);
     }
-    const unsigned long long frm = __ballot(fr && g == 3);     // same rows as the g == 0 lanes
-    fraud += __popcll(frm);
-    rows += (unsigned)min(kTileRows, n - t * kTileRows);
     sw.fraud += __popcll(__ballot(sf && g == 3));
-    sw.both += __popcll(__ballot(sf && fr && g == 3));
-    const float am_g3 = (valid && g == 3) ? amount : -__builtin_inff();
-    hist_lanes_add(hl, __shfl(am_g3, 48 + c));
-    if (frm) {                                                   // rare: fraud rows' buckets
-      if (fr && g == 3) atomicAdd(&epi.hist[kNB + amount_bucket_fast(amount)], 1u);
-      flag_push(a, fls, frm, fr && g == 3, row, lane);
-    }
+    sw.both += __popcll(__ballot(sf && o.fr && g == 3));
+    if (o.m) flag_push(a, fls, o.m, o.fr && g == 3, row, lane);
   };
   // steady state: both tiles of the pair exist
   const int full_end = ntiles - tstride;
@@ -137,13 +127,9 @@ __global__ __launch_bounds__(64 * kShadowWaves) void score_shadow_kernel(ccfd_sh
     finish(p, q, __uint_as_float(r0.v.w), tile);
   }
   if (a.flag_idx != nullptr) flag_flush(a, fls, lane);
-  psum = wave_sum_u64(psum);
   hist_lanes_commit(epi, hl, g, c);
-  if (lane == 0) {
-    atomicAdd(&epi.fraud, fraud);
-    atomicAdd(&epi.rows, rows);
-    atomicAdd(&epi.psum_e6, psum);
-  }
+  const unsigned rows = w.rows;
+  tile_wave_commit(epi, w, lane);
   shadow_wave_commit(sh, sw, rows, lane);
   epi_flush_ballot(epi, a.counters);                    // barrier first, then the champion's atomics
   if (tid == 2 * kNB + 1) shadow_flush(sh, a.counters);
@@ -189,38 +175,22 @@ __global__ __launch_bounds__(256) void persist_shadow_kernel(ccfd_persist_shadow
     __syncthreads();
     if (s_cmd) break;
 
-    const unsigned long long item = s_item;
     const ccfd_persist_desc dsc = sdesc;
-    const int chunk = (int)(item % (unsigned long long)C);
-    const int slot = (int)(dsc.seq % (unsigned long long)a.ring);
-    const int n = dsc.n;
     const int kTilesPerWave = a.tiles_per_wave;
-    const int tile0 = chunk * (4 * kTilesPerWave) + wave;      // wave w: tiles tile0 + 4k
-    if (chunk == 0 && tid == 0)                                // K7: micro-batch start (item 0 claimed first)
-      __hip_atomic_store(&a.dev->tstart[slot], wall_clock64(), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned char* xw = reinterpret_cast<const unsigned char*>(dsc.x);
-    unsigned nf_w = 0, nv_w = 0;
-    unsigned long long ps_w = 0;
+    const PersistItem it = persist_item(a, dsc, s_item, C, 4 * kTilesPerWave, wave, tid == 0);   // K7: item 0 is claimed first
+    const int slot = it.slot, n = it.n, tile0 = it.u0;         // wave w: tiles tile0 + 4k
+    const unsigned char* xw = it.xb;
+    TileWave w;
     ShadowAcc sw;
-    // per-tile epilogue: the champion's as in persist_kernel, then the challenger's counters
+    // per-tile epilogue: the champion's as in persist_kernel (tile_core.h), then the challenger's counters
     auto finish = [&](float p, float q, float amount, int tile) __attribute__((always_inline)) {
       const int row = tile * kTileRows + c;
-      const bool valid = row < n;
-      const bool fr = valid && (p >= a.threshold);
-      const bool sf = valid && (q >= a.threshold);
-      if (valid && g == 0) {
-        if (dsc.proba) st_g(dsc.proba + row, p);
-        if (dsc.route) st_g(dsc.route + row, (uint8_t)(fr ? 1 : 0));
-        ps_w += (unsigned long long)(p * 1e6f + 0.5f);
-        shadow_row(sw, p, q);
-      }
-      const unsigned long long m = __ballot(fr && g == 0);
-      nf_w += __popcll(m);
-      nv_w += __popcll(__ballot(valid && g == 0));
+      const TileRowOut o = tile_row_epilogue(epi, w, p, p >= a.threshold, amount, row, n, g, dsc.proba, dsc.route);
+      const bool sf = o.valid && (q >= a.threshold);
+      if (o.valid && g == 0) shadow_row(sw, p, q);
       sw.fraud += __popcll(__ballot(sf && g == 0));
-      sw.both += __popcll(__ballot(sf && fr && g == 0));
-      if (valid && g == 3) atomicAdd(&epi.hist[(fr ? kNB : 0) + amount_bucket(amount)], 1u);
-      persist_emit_flagged(a, dsc, slot, m, fr && g == 0, row, lane);
+      sw.both += __popcll(__ballot(sf && o.fr && g == 0));
+      persist_emit_flagged(a, dsc, slot, o.m, o.fr && g == 0, row, lane);
     };
     auto full_item = [&](auto kT) __attribute__((always_inline)) {
       constexpr int T = decltype(kT)::value;
@@ -246,12 +216,8 @@ __global__ __launch_bounds__(256) void persist_shadow_kernel(ccfd_persist_shadow
     } else {
       full_item(std::integral_constant<int, 8>{});
     }
-    ps_w = wave_sum_u64(ps_w);
-    if (lane == 0 && nv_w) {
-      atomicAdd(&epi.fraud, nf_w);
-      atomicAdd(&epi.rows, nv_w);
-      atomicAdd(&epi.psum_e6, ps_w);
-    }
+    const unsigned nv_w = w.rows;
+    tile_item_commit(epi, w, lane);
     shadow_wave_commit(sh, sw, nv_w, lane);
     // the item's challenger counters, then LDS reset for the next item: persist_item_done's
     // barriers and its vmcnt(0) drain order both before the item's ticket and the next claim

@@ -1,6 +1,7 @@
 // Streaming body shared by the W64 wire kernels (MLP, LR): 16-row tiles per wave with a
-// branch-free prefetch ring, the per-tile epilogue (outputs, counters, lane-spread amount
-// histogram, compacted fraud list) and the workgroup flush.  The model math is a Scorer:
+// branch-free prefetch ring, the per-tile epilogue (tile_row_epilogue_lanes of tile_core.h:
+// outputs, counters, lane-spread amount histogram; then the compacted fraud list) and the
+// workgroup flush.  The model math is a Scorer:
 //   static constexpr int kLds;                       LDS bytes the scorer stages (blob copy)
 //   void stage(const ccfd_score_args&, char* lds, int tid, int nthreads);   before the barrier
 //   void lanes(const char* lds, const ccfd_score_args&, int g);            after the barrier
@@ -11,6 +12,7 @@
 #pragma once
 #include "common.h"
 #include "rules.h"
+#include "tile_core.h"
 
 namespace ccfd {
 
@@ -51,8 +53,7 @@ __device__ __forceinline__ void wire_stream_body(const ccfd_score_args& a, int b
 
   const float thr = a.threshold;
   FlagStage fls{flbuf[wave], 0u};
-  unsigned fraud = 0, rows = 0;
-  unsigned long long psum = 0;
+  TileWave w;
   HistLanes hl;
   hist_lanes_init(hl, g);
   // routing rules (when configured) read the tile's features, so they are evaluated while
@@ -69,22 +70,10 @@ __device__ __forceinline__ void wire_stream_body(const ccfd_score_args& a, int b
   };
   auto finish = [&](float p, float amount, int t, bool rf) __attribute__((always_inline)) {
     const int row = t * kTileRows + c;
-    const bool valid = row < n;
-    const bool fr = valid && (kR ? rf : (p >= thr));
-    if (valid && g == 0) {
-      if (a.proba) st_g(a.proba + row, p);
-      if (a.route) st_g(a.route + row, (uint8_t)(fr ? 1 : 0));
-      psum += (unsigned)(p * 1e6f + 0.5f);
-    }
-    const unsigned long long frm = __ballot(fr && g == 3);     // same rows as the g == 0 lanes
-    fraud += __popcll(frm);
-    rows += (unsigned)min(kTileRows, n - t * kTileRows);
-    const float am_g3 = (valid && g == 3) ? amount : -__builtin_inff();
-    hist_lanes_add(hl, __shfl(am_g3, 48 + c));
-    if (frm) {                                                   // rare: fraud rows' buckets
-      if (fr && g == 3) atomicAdd(&epi.hist[kNB + amount_bucket_fast(amount)], 1u);
-      if (a.flags & CCFD_ARG_FLAG_DIRECT) emit_flagged(a, fr && g == 3, row);
-      else flag_push(a, fls, frm, fr && g == 3, row, lane);
+    const TileRowOut o = tile_row_epilogue_lanes(epi, w, hl, p, kR ? rf : (p >= thr), amount, t, n, g, c, a.proba, a.route);
+    if (o.m) {                                                   // rare
+      if (a.flags & CCFD_ARG_FLAG_DIRECT) emit_flagged(a, o.fr && g == 3, row);
+      else flag_push(a, fls, o.m, o.fr && g == 3, row, lane);
     }
   };
   // steady state: the kPf strided tiles of a round all exist
@@ -123,11 +112,11 @@ __device__ __forceinline__ void wire_stream_body(const ccfd_score_args& a, int b
       if (valid) {
         if (a.proba) st_g(a.proba + row, p);
         if (a.route) st_g(a.route + row, (uint8_t)(fr ? 1 : 0));
-        psum += (unsigned)(p * 1e6f + 0.5f);
+        w.psum += (unsigned)(p * 1e6f + 0.5f);
       }
       const unsigned long long frm = __ballot(fr);
-      fraud += __popcll(frm);
-      rows += __popcll(__ballot(valid));
+      w.fraud += __popcll(frm);
+      w.rows += __popcll(__ballot(valid));
       const float amv = valid ? ams : -__builtin_inff();
 #pragma unroll
       for (int j = 0; j < kNB - 1; ++j) hgt[j] += __popcll(__ballot(amv > kB[j]));
@@ -177,7 +166,6 @@ __device__ __forceinline__ void wire_stream_body(const ccfd_score_args& a, int b
     tile += tstride;
   }
   if (a.flag_idx != nullptr) flag_flush(a, fls, lane);
-  psum = wave_sum_u64(psum);
   hist_lanes_commit(epi, hl, g, c);
   if constexpr (kQuadPath) {
     if (lane == 0) {
@@ -186,11 +174,7 @@ __device__ __forceinline__ void wire_stream_body(const ccfd_score_args& a, int b
         if (hgt[j]) atomicAdd(&epi.hgt[j], hgt[j]);
     }
   }
-  if (lane == 0) {
-    atomicAdd(&epi.fraud, fraud);
-    atomicAdd(&epi.rows, rows);
-    atomicAdd(&epi.psum_e6, psum);
-  }
+  tile_wave_commit(epi, w, lane);
   epi_flush_ballot(epi, a.counters);
   signal_done(a, (unsigned)nblk);
 }
