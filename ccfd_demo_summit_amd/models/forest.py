@@ -61,6 +61,7 @@ class TreeEnsemble:
     base: float = 0.0
     link: str = "sigmoid"
     kind: str = "forest"
+    cover: Optional[np.ndarray] = None    # float32 [n_nodes] background weight of every node (explanations)
 
     def __post_init__(self):
         self.feat = np.ascontiguousarray(self.feat, np.int32).reshape(-1)
@@ -115,6 +116,12 @@ class TreeEnsemble:
             node, tree = np.concatenate([c, c + 1]), np.concatenate([tree, tree])
         self.tree_depth = depth
         self.node_tree = owner
+        if self.cover is not None:
+            self.cover = np.ascontiguousarray(self.cover, np.float32).reshape(-1)
+            if self.cover.size != n:
+                raise ValueError(f"cover has {self.cover.size} entries for {n} nodes")
+            if not np.isfinite(self.cover).all() or (self.cover < 0).any():
+                raise ValueError("cover must be finite and >= 0")
 
     # ------------------------------------------------------------------ shape
     @property
@@ -158,11 +165,30 @@ class TreeEnsemble:
         z = self.raw_score(X)
         return sigmoid(z) if self.link == "sigmoid" else np.clip(z, 0.0, 1.0).astype(np.float32)
 
+    def fit_cover(self, X: np.ndarray) -> "TreeEnsemble":
+        """A copy whose ``cover`` counts the rows of ``X`` (float32 [n,30]) at every node: the
+        background of the Shapley attributions (models/explain_forest.py).  Counted in int64."""
+        X = np.asarray(X, np.float32)
+        if X.ndim != 2 or X.shape[1] != N_FEATURES:
+            raise ValueError("background rows must be float32 [n, 30]")
+        count = np.zeros(self.n_nodes, np.int64)
+        cur = np.broadcast_to(self.root[None, :], (X.shape[0], self.n_trees)).astype(np.int64)
+        rows = np.arange(X.shape[0])[:, None]
+        count += np.bincount(cur.reshape(-1), minlength=self.n_nodes)
+        for _ in range(self.depth):
+            inner = ~self.leaf[cur]
+            right = X[rows, self.feat[cur]] > self.value[cur]
+            cur = np.where(inner, self.child[cur] + right, cur)
+            count += np.bincount(cur[inner], minlength=self.n_nodes)
+        return TreeEnsemble(self.feat, self.value, self.child, self.leaf, self.root, self.base, self.link,
+                            cover=count.astype(np.float32))
+
     # ------------------------------------------------------------------ constructors
     @classmethod
     def from_oblivious(cls, m: ObliviousGBDT) -> "TreeEnsemble":
         """Each oblivious tree expanded into a complete general tree with identical outputs
-        (level l of the tree tests split l; NaN thresholds carry over: ``x > NaN`` is false)."""
+        (level l of the tree tests split l; NaN thresholds carry over: ``x > NaN`` is false).  The
+        cover of the oblivious model, if it has one, carries over: a node's is the sum of its leaves'."""
         T, D = m.n_trees, m.depth
         per = (2 << D) - 1
         L = 1 << D
@@ -183,8 +209,15 @@ class TreeEnsemble:
         value[:, is_leaf] = m.leaves[:, rev[pos[is_leaf]]]
         off = np.arange(T, dtype=np.int64)[:, None] * per
         child[:] = (off + ((2 << lvl) - 1 + 2 * pos)[None, :]).astype(np.int32)
+        cover = None
+        if getattr(m, "cover", None) is not None:
+            # leaf cover in path order, then every level is the pairwise sum of the one below
+            levels = [np.asarray(m.cover, np.float64)[:, rev]]
+            for _ in range(D):
+                levels.append(levels[-1][:, 0::2] + levels[-1][:, 1::2])
+            cover = np.concatenate(levels[::-1], axis=1).astype(np.float32).reshape(-1)
         return cls(feat.reshape(-1), value.reshape(-1), child.reshape(-1), np.tile(is_leaf, T),
-                   (off[:, 0]).astype(np.int32), float(m.base), "sigmoid")
+                   (off[:, 0]).astype(np.int32), float(m.base), "sigmoid", cover=cover)
 
     @classmethod
     def random_init(cls, n_trees: int = 16, max_depth: int = 8, p_leaf: float = 0.2, seed: int = 0,
@@ -298,13 +331,17 @@ class TreeEnsemble:
         return m
 
     def state_dict(self) -> dict:
-        return {"forest.feat": self.feat, "forest.value": self.value, "forest.child": self.child,
-                "forest.leaf": self.leaf.astype(np.uint8), "forest.root": self.root,
-                "forest.base": np.array([self.base], np.float64),
-                "forest.link": np.array([LINKS.index(self.link)], np.int32)}
+        st = {"forest.feat": self.feat, "forest.value": self.value, "forest.child": self.child,
+              "forest.leaf": self.leaf.astype(np.uint8), "forest.root": self.root,
+              "forest.base": np.array([self.base], np.float64),
+              "forest.link": np.array([LINKS.index(self.link)], np.int32)}
+        if self.cover is not None:
+            st["forest.cover"] = self.cover
+        return st
 
     @classmethod
     def from_state_dict(cls, st: dict) -> "TreeEnsemble":
         return cls(st["forest.feat"], st["forest.value"], st["forest.child"], np.asarray(st["forest.leaf"]) != 0,
                    st["forest.root"], float(np.asarray(st["forest.base"]).reshape(-1)[0]),
-                   LINKS[int(np.asarray(st["forest.link"]).reshape(-1)[0])])
+                   LINKS[int(np.asarray(st["forest.link"]).reshape(-1)[0])],
+                   cover=st["forest.cover"] if "forest.cover" in st else None)

@@ -16,6 +16,8 @@ Accepted estimators, fitted on the 30 transaction columns (Time, V1..V28, Amount
   leaf value = class-1 fraction of ``tree_.value`` / T, identity link, base 0;
 * ``GradientBoostingClassifier`` (log-loss, default prior init) -> ``TreeEnsemble``:
   base = log(prior_1 / prior_0), leaf value = learning_rate * value, sigmoid link.
+  Every tree model carries ``tree_.weighted_n_node_samples`` as the ensemble's ``cover``, the
+  background of its Shapley attributions (models/explain_forest.py).
 
 Trees take RAW features: a ``StandardScaler`` in front of a tree model is refused (the tree
 kernels have no normaliser; refit the trees on raw columns, they are scale invariant).
@@ -84,8 +86,9 @@ _TREE_MODELS = _FORESTS + ("GradientBoostingClassifier",)
 def _sk_trees(trees, leaf_value) -> tuple:
     """Concatenate sklearn ``tree_`` objects into TreeEnsemble arrays.  sklearn stores children
     anywhere (depth-first); each inner node's two children get a fresh adjacent pair here,
-    in breadth-first order per tree, so child indices point forward."""
-    feat, value, child, leaf, root = [], [], [], [], []
+    in breadth-first order per tree, so child indices point forward.  Returns (the five node
+    arrays, cover): ``weighted_n_node_samples`` re-indexed like the nodes."""
+    feat, value, child, leaf, root, cover = [], [], [], [], [], []
     for k, tr in enumerate(trees):
         left, right = tr.children_left, tr.children_right
         thr = f32_floor(tr.threshold)
@@ -110,8 +113,9 @@ def _sk_trees(trees, leaf_value) -> tuple:
                 for _ in range(2):
                     feat.append(0); value.append(0.0); child.append(0); leaf.append(True)
             i += 1
+        cover.append(np.asarray(tr.weighted_n_node_samples, np.float64)[order])
     return (np.array(feat, np.int32), np.array(value, np.float32), np.array(child, np.int32),
-            np.array(leaf, bool), np.array(root, np.int32))
+            np.array(leaf, bool), np.array(root, np.int32)), np.concatenate(cover).astype(np.float32)
 
 
 def _forest(est: Any, name: str) -> TreeEnsemble:
@@ -124,7 +128,8 @@ def _forest(est: Any, name: str) -> TreeEnsemble:
         def frac(_k, tr):                            # class-1 fraction of the node's samples, / T
             v = np.asarray(tr.value, np.float64)[:, 0, :]
             return v[:, 1] / v.sum(1) / T
-        return TreeEnsemble(*_sk_trees(trees, frac), 0.0, "identity")
+        arrays, cover = _sk_trees(trees, frac)
+        return TreeEnsemble(*arrays, 0.0, "identity", cover=cover)
     loss = getattr(est, "loss", "log_loss")
     if loss not in ("log_loss", "deviance"):
         raise ValueError(f"GradientBoostingClassifier loss {loss!r}: only log-loss maps onto the sigmoid link")
@@ -141,8 +146,8 @@ def _forest(est: Any, name: str) -> TreeEnsemble:
                          "init (init=None) or init='zero' is imported")
     trees = [e.tree_ for e in np.asarray(est.estimators_)[:, 0]]
     lr = float(est.learning_rate)
-    return TreeEnsemble(*_sk_trees(trees, lambda _k, tr: lr * np.asarray(tr.value, np.float64)[:, 0, 0]),
-                        base, "sigmoid")
+    arrays, cover = _sk_trees(trees, lambda _k, tr: lr * np.asarray(tr.value, np.float64)[:, 0, 0])
+    return TreeEnsemble(*arrays, base, "sigmoid", cover=cover)
 
 
 def from_sklearn(est: Any) -> Any:

@@ -8,7 +8,9 @@ What is read:
   ``left_children == -1`` and its value in ``split_conditions``;
 * ``learner.learner_model_param.base_score``: a probability (plain ``"5E-1"`` or bracketed
   ``"[5E-1]"``), so base = logit(base_score);
-* ``learner.objective.name``: ``binary:logistic`` only (sigmoid link).
+* ``learner.objective.name``: ``binary:logistic`` only (sigmoid link);
+* ``trees[*].sum_hessian``, when every tree has it: the ensemble's ``cover`` (the background of
+  its Shapley attributions, models/explain_forest.py); otherwise the ensemble has none.
 
 XGBoost sends a row LEFT on ``x < t`` with a float32 ``t``; the kernels go right on
 ``x > thr``.  ``thr = nextafter(t, -inf)`` makes ``x > thr`` <=> ``x >= t`` for every float32
@@ -79,6 +81,7 @@ def from_xgboost_json(doc: Union[str, Dict[str, Any]]) -> TreeEnsemble:
     base = _base_score(lmp.get("base_score", "5E-1"))
 
     feat, value, child, leaf, root = [], [], [], [], []
+    cover = [] if all("sum_hessian" in tree for tree in trees) else None
     for t, tree in enumerate(trees):
         left = [int(v) for v in tree["left_children"]]
         right = [int(v) for v in tree["right_children"]]
@@ -111,5 +114,11 @@ def from_xgboost_json(doc: Union[str, Dict[str, Any]]) -> TreeEnsemble:
                 for _ in range(2):
                     feat.append(0); value.append(0.0); child.append(0); leaf.append(True)
             i += 1
+        if cover is not None:
+            hess = np.asarray(tree["sum_hessian"], np.float64)
+            if hess.size != len(left):
+                raise ValueError(f"tree {t}: sum_hessian has {hess.size} entries for {len(left)} nodes")
+            cover.append(hess[order])
     return TreeEnsemble(np.array(feat, np.int32), np.array(value, np.float32), np.array(child, np.int32),
-                        np.array(leaf, bool), np.array(root, np.int32), base, "sigmoid")
+                        np.array(leaf, bool), np.array(root, np.int32), base, "sigmoid",
+                        cover=None if cover is None else np.concatenate(cover).astype(np.float32))

@@ -80,6 +80,12 @@ class GbdtExplainArgs(C.Structure):      # ccfd_gbdt_explain_args
                 ("blob_bytes", C.c_int64), ("trees", C.c_int32), ("depth", C.c_int32)]
 
 
+class ForestExplainArgs(C.Structure):    # ccfd_forest_explain_args
+    _fields_ = [("rows", C.c_void_p), ("blob", C.c_void_p), ("phi", C.c_void_p), ("workspace", C.c_void_p),
+                ("n", C.c_int64), ("blob_bytes", C.c_int64), ("workspace_bytes", C.c_int64),
+                ("paths", C.c_int32), ("width", C.c_int32), ("slices", C.c_int32), ("rec_words", C.c_int32)]
+
+
 DRIFT_COLS, DRIFT_CELLS = 31, 256       # ccfd_abi.h CCFD_DRIFT_*
 
 
@@ -165,6 +171,10 @@ def lib() -> C.CDLL:
         L.ccfd_gbdt_update_launch.restype = C.c_int
         L.ccfd_gbdt_explain_launch.argtypes = [C.POINTER(GbdtExplainArgs), C.c_void_p]
         L.ccfd_gbdt_explain_launch.restype = C.c_int
+        L.ccfd_forest_explain_launch.argtypes = [C.POINTER(ForestExplainArgs), C.c_void_p]
+        L.ccfd_forest_explain_launch.restype = C.c_int
+        L.ccfd_forest_explain_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
+        L.ccfd_forest_explain_workspace_bytes.restype = C.c_int64
         L.ccfd_drift_hist_launch.argtypes = [C.POINTER(DriftHistArgs), C.c_void_p]
         L.ccfd_drift_hist_launch.restype = C.c_int
         L.ccfd_forest_blob_changed.argtypes = [C.c_void_p]

@@ -14,8 +14,8 @@ import numpy as np
 import torch
 
 from ._lib import (ARG_WIRE_G20, ARG_WIRE_G32, ARG_WIRE_W64, BIN_FORMATS, DRIFT_CELLS, DRIFT_COLS, GBDT_MAX_SPLITS,
-                   MODEL_IDS, N_COUNTER_SLOTS, DriftHistArgs, GbdtExplainArgs, GbdtHistArgs, GbdtUpdateArgs, ScoreArgs,
-                   ShadowArgs, check, lib)
+                   MODEL_IDS, N_COUNTER_SLOTS, DriftHistArgs, ForestExplainArgs, GbdtExplainArgs, GbdtHistArgs,
+                   GbdtUpdateArgs, ScoreArgs, ShadowArgs, check, lib)
 
 N_FEATURES = 30
 ROW_BYTES = {"f32": 4 * N_FEATURES, "w64": 64, "g32": 32, "g20": 20}
@@ -296,22 +296,48 @@ def gbdt_apply_tree(rows: torch.Tensor, raw: torch.Tensor, leaf_val: torch.Tenso
     return raw, grad, hess
 
 
-# ---------------------------------------------------------------------------- GBDT explanations
+# ---------------------------------------------------------------------------- explanations
 class DeviceExplainer:
-    """The 'GBX1' table of an oblivious GBDT with cover (``ObliviousGBDT.fit_cover``) resident
-    in HBM, for ``explain_gbdt``.  ``bins``: the 8-bit ``BinSpec`` the G32 rows were encoded
-    with (default: the model's own table).  ``base_value + phi.sum(1)`` is the raw score."""
+    """The explain table of a tree model with cover resident in HBM: the 'GBX1' table of an
+    oblivious GBDT (``ObliviousGBDT.fit_cover``) for ``explain_gbdt``, or the 'FRX1' path table of
+    a general ensemble (kind "forest"; ``TreeEnsemble.fit_cover`` or an importer's cover) for
+    ``explain_forest``, together with the workspace that kernel's small batches need.  ``bins``:
+    the 8-bit ``BinSpec`` the G32 rows were encoded with (default: the model's own table).
+    ``base_value + phi.sum(1)`` is the raw score."""
 
     def __init__(self, model, bins=None, device: torch.device | str | int = "cuda"):
-        from ..models.explain import ExplainTable, base_value
-        if getattr(model, "kind", None) != "gbdt":
-            raise ValueError(f"no explain kernel for model kind {getattr(model, 'kind', None)!r} (oblivious GBDT only)")
+        self.kind = getattr(model, "kind", None)
+        if self.kind not in ("gbdt", "forest"):
+            raise ValueError(f"no explain kernel for model kind {self.kind!r} (oblivious GBDT and general tree "
+                             "ensembles only)")
         self.bins = bins if bins is not None else model.bin_spec()
-        packed = ExplainTable.pack(model, self.bins)
+        if self.kind == "gbdt":
+            from ..models.explain import ExplainTable, base_value
+            packed = ExplainTable.pack(model, self.bins)
+            self.base_value = base_value(model)
+        else:
+            from ..models.explain_forest import ForestExplainTable, forest_base_value
+            packed = ForestExplainTable.pack(model, self.bins)
+            self.base_value = forest_base_value(model)
+            self.paths, self.width = (int(v) for v in np.frombuffer(packed, np.int32, 2, 8))
+            self.slices, self.rec_words = (int(v) for v in np.frombuffer(packed, np.int32, 2, 24))
+            self._workspace = {}         # stream handle -> float32 tensor of partial sums
         self.blob = torch.from_numpy(np.frombuffer(packed, np.uint8).copy()).to(device)
         self.trees, self.depth = model.n_trees, model.depth
-        self.base_value = base_value(model)
         self.device = self.blob.device
+
+    def workspace(self, n: int, stream: torch.cuda.Stream) -> Optional[torch.Tensor]:
+        """The partial-sum buffer ``explain_forest`` needs for ``n`` rows on ``stream`` (``None``
+        when the launch needs none).  One buffer a stream, grown on demand and kept."""
+        need = int(lib().ccfd_forest_explain_workspace_bytes(int(n), self.slices))
+        if need == 0:
+            return None
+        ws = self._workspace.get(stream.cuda_stream)
+        if ws is None or ws.numel() * 4 < need:
+            ws = torch.empty(need // 4, dtype=torch.float32, device=self.device)
+            self._workspace[stream.cuda_stream] = ws
+        ws.record_stream(stream)
+        return ws
 
     def explain(self, X: np.ndarray) -> Tuple[np.ndarray, float]:
         """float32 [n,30] host rows -> (phi float32 [n,30] numpy, base_value)."""
@@ -319,16 +345,14 @@ class DeviceExplainer:
         if X.ndim != 2 or X.shape[1] != N_FEATURES:
             raise ValueError("X must be float32 [n, 30]")
         rows = torch.from_numpy(np.ascontiguousarray(self.bins.encode(X))).to(self.device)
-        return explain_gbdt(self, rows).cpu().numpy(), self.base_value
+        fn = explain_gbdt if self.kind == "gbdt" else explain_forest
+        return fn(self, rows).cpu().numpy(), self.base_value
 
 
-def explain_gbdt(ex: DeviceExplainer, rows: torch.Tensor, out: Optional[torch.Tensor] = None,
-                 stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
-    """Exact per-feature Shapley values (margin space) of G32 ``rows`` ([n,32] u8, CUDA) under
-    ``ex``'s model (csrc/kernels/explain_gbdt.hip; definition in docs/EXPLAIN.md): returns
-    ``phi`` float32 ``[n, 30]`` (``out=`` reuses such a tensor).  A row whose stamp differs from
-    the table's gets NaN in all 30 entries; a feature no tree tests gets exactly 0.  The
-    summation order is fixed: two runs give identical bits."""
+def _explain_out(ex: DeviceExplainer, kind: str, rows: torch.Tensor, out: Optional[torch.Tensor]) -> torch.Tensor:
+    if getattr(ex, "kind", None) != kind:
+        raise ValueError(f"the explainer holds a {getattr(ex, 'kind', None)!r} table: use "
+                         f"explain_{'gbdt' if kind == 'forest' else 'forest'} (or DeviceExplainer.explain)")
     n = _g32_rows(rows)
     if rows.device != ex.blob.device:
         raise ValueError("rows must be on the explainer's device")
@@ -338,11 +362,44 @@ def explain_gbdt(ex: DeviceExplainer, rows: torch.Tensor, out: Optional[torch.Te
     elif not out.is_cuda or out.device != rows.device or out.dtype != torch.float32 or tuple(out.shape) != shape or \
             not out.is_contiguous():
         raise ValueError(f"out must be a contiguous CUDA float32 tensor of shape {list(shape)} on the rows' device")
+    return out
+
+
+def explain_gbdt(ex: DeviceExplainer, rows: torch.Tensor, out: Optional[torch.Tensor] = None,
+                 stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """Exact per-feature Shapley values (margin space) of G32 ``rows`` ([n,32] u8, CUDA) under
+    ``ex``'s model (csrc/kernels/explain_gbdt.hip; definition in docs/EXPLAIN.md): returns
+    ``phi`` float32 ``[n, 30]`` (``out=`` reuses such a tensor).  A row whose stamp differs from
+    the table's gets NaN in all 30 entries; a feature no tree tests gets exactly 0.  The
+    summation order is fixed: two runs give identical bits."""
+    out = _explain_out(ex, "gbdt", rows, out)
     a = GbdtExplainArgs()
     a.rows, a.blob, a.phi = rows.data_ptr(), ex.blob.data_ptr(), out.data_ptr()
-    a.n, a.blob_bytes, a.trees, a.depth = n, ex.blob.numel(), ex.trees, ex.depth
+    a.n, a.blob_bytes, a.trees, a.depth = rows.shape[0], ex.blob.numel(), ex.trees, ex.depth
     s = stream if stream is not None else torch.cuda.current_stream(rows.device)
     check(lib().ccfd_gbdt_explain_launch(C.byref(a), C.c_void_p(s.cuda_stream)), "ccfd_gbdt_explain_launch")
+    return out
+
+
+def explain_forest(ex: DeviceExplainer, rows: torch.Tensor, out: Optional[torch.Tensor] = None,
+                   stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """``explain_gbdt``'s contract for a general tree ensemble (csrc/kernels/explain_forest.hip):
+    exact per-feature Shapley values of the raw score of G32 ``rows`` ([n,32] u8, CUDA) under
+    ``ex``'s ensemble, ``phi`` float32 ``[n, 30]`` (``out=`` reuses such a tensor).  A row whose
+    stamp differs from the table's gets NaN in all 30 entries; a feature that no split with
+    cover tests gets exactly 0.  Every sum has a fixed order that depends on neither ``n`` nor
+    the other rows: a row explained alone gets the bits it gets in a batch.  Small batches
+    under a large table use ``ex.workspace`` on the launch's stream."""
+    out = _explain_out(ex, "forest", rows, out)
+    n = rows.shape[0]
+    s = stream if stream is not None else torch.cuda.current_stream(rows.device)
+    ws = ex.workspace(n, s)
+    a = ForestExplainArgs()
+    a.rows, a.blob, a.phi = rows.data_ptr(), ex.blob.data_ptr(), out.data_ptr()
+    a.workspace, a.workspace_bytes = (ws.data_ptr(), ws.numel() * 4) if ws is not None else (None, 0)
+    a.n, a.blob_bytes = n, ex.blob.numel()
+    a.paths, a.width, a.slices, a.rec_words = ex.paths, ex.width, ex.slices, ex.rec_words
+    check(lib().ccfd_forest_explain_launch(C.byref(a), C.c_void_p(s.cuda_stream)), "ccfd_forest_explain_launch")
     return out
 
 

@@ -5,8 +5,9 @@
                     (pageable host input is staged by DMA; results come back pinned).
 
 Both return ``(proba_1 float32[n], route uint8[n])`` with route = proba >= threshold.
-``explain(X)`` (oblivious GBDT with cover only; anything else raises ``ValueError``) returns
-``(phi float32/64 [n,30], base_value)``, the exact Shapley attributions of docs/EXPLAIN.md.
+``explain(X)`` (an oblivious GBDT or a general tree ensemble, with cover; anything else raises
+``ValueError``) returns ``(phi float32/64 [n,30], base_value)``, the exact Shapley attributions
+of docs/EXPLAIN.md.
 ``set_drift(reference)`` (oblivious GBDT only, likewise) makes every later ``score(X)`` batch also
 count its rows, binned against the model's table, into a drift window; ``drift()`` reports it
 (docs/DRIFT.md).
@@ -66,14 +67,21 @@ class CpuScorer:
 
     def explain(self, X: np.ndarray) -> Tuple[np.ndarray, float]:
         _explainable(self.model)
+        if self.model.kind == "forest":
+            from ..models.explain_forest import shapley_forest
+            return shapley_forest(self.model, np.asarray(X, np.float32))
         from ..models.explain import shapley_oblivious
         return shapley_oblivious(self.model, np.asarray(X, np.float32))
 
 
 def _explainable(model) -> None:
-    if getattr(model, "kind", None) != "gbdt":
-        raise ValueError(f"model kind {getattr(model, 'kind', None)!r} has no explanation "
-                         "(exact Shapley values exist for the oblivious GBDT only)")
+    kind = getattr(model, "kind", None)
+    if kind not in ("gbdt", "forest"):
+        raise ValueError(f"model kind {kind!r} has no explanation "
+                         "(exact Shapley values exist for the tree models only)")
+    if kind == "forest" and getattr(model, "cover", None) is None:
+        raise ValueError("the ensemble has no cover (background weight of every node): call fit_cover(X) first, "
+                         "or import a model that carries one")
 
 
 def _drift_bins(model, reference):
@@ -139,7 +147,8 @@ class GpuScorer:
             return self._drift[0].report(reset=reset)
 
     def explain(self, X: np.ndarray) -> Tuple[np.ndarray, float]:
-        """csrc/kernels/explain_gbdt.hip on the rows binned against the model's own table."""
+        """csrc/kernels/explain_gbdt.hip (oblivious GBDT) or explain_forest.hip (general trees) on
+        the rows binned against the model's own table."""
         _explainable(self.model)
         with self._lock:
             if self._explainer is None:

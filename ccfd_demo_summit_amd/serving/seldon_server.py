@@ -8,7 +8,8 @@ Endpoints (port 8000 like ``SELDON_URL=http://modelfull-modelfull:8000``, router
                                accepts form field ``json=``
   POST /api/v0.1/explain, /api/v1.0/explain, /explain
                                per-feature Shapley values of the same request body (oblivious
-                               GBDT with cover; docs/EXPLAIN.md); 400 for any other model
+                               GBDT or general tree ensemble, with cover; docs/EXPLAIN.md);
+                               400 for any other model
   GET  /api/v0.1/drift, /api/v1.0/drift, /drift
                                PSI per feature of the rows predicted so far against the drift
                                reference (docs/DRIFT.md); POST {"reset": true} starts the next

@@ -234,6 +234,42 @@ typedef struct ccfd_gbdt_explain_args {
 int ccfd_gbdt_explain_launch(const ccfd_gbdt_explain_args* a, void* stream);
 
 // ---------------------------------------------------------------------------
+// Exact per-feature Shapley values of a general tree ensemble on G32 rows (explain_forest.hip;
+// models/explain_forest.py holds the definition, the CPU oracles and the packer of the 'FRX1'
+// blob: one record per root-to-leaf path).  phi[i][j] is the attribution of feature j to the raw
+// score of row i; the blob's base_value + sum_j phi[i][j] is the row's raw score.  A row whose
+// stamp (byte 31) differs from the blob's gets quiet NaN in all 30 outputs.  `paths`, `width`,
+// `slices`, `rec_words` and `blob_bytes` repeat the header of the blob the caller packed (the
+// launch cannot read device memory): width is 4, 8, 12 or 16, slices 1..16, and blob_bytes >=
+// the FRX1 size of that shape.  n >= 0; n == 0 returns without a launch.
+// A batch of fewer than CCFD_FRX_SPLIT_BLOCKS * 64 rows under a blob of more than one slice
+// runs its slices on grid.y, writes their partial sums into `workspace`
+// (ccfd_forest_explain_workspace_bytes(n, slices) bytes, 0 when the launch needs none) and adds
+// them in slice order in a second kernel; a larger batch walks the slices inside one workgroup
+// and adds them in the same order.  Every sum has a fixed order that depends neither on n nor
+// on the other rows: a row explained alone gets the bits it gets in any batch.
+#define CCFD_FRX_MAX_WIDTH 16
+#define CCFD_FRX_MAX_SLICES 16
+#define CCFD_FRX_WAVES 4
+#define CCFD_FRX_RULE_BYTES (8 * 2 * 8 * 8)
+#define CCFD_FRX_SPLIT_BLOCKS 256
+typedef struct ccfd_forest_explain_args {
+  const uint8_t* rows;   // device [n][32], 16-byte aligned
+  const void* blob;      // device FRX1 blob, 16-byte aligned
+  float* phi;            // device out [n][30]
+  float* workspace;      // device [slices][n][30] partial sums, or null when none is needed
+  int64_t n;
+  int64_t blob_bytes;
+  int64_t workspace_bytes;
+  int32_t paths;
+  int32_t width;
+  int32_t slices;
+  int32_t rec_words;
+} ccfd_forest_explain_args;   // 72 bytes
+int ccfd_forest_explain_launch(const ccfd_forest_explain_args* a, void* stream);
+int64_t ccfd_forest_explain_workspace_bytes(int64_t n, int32_t slices);
+
+// ---------------------------------------------------------------------------
 // Per-feature bin counts of G32 / G20 rows, for drift detection (drift_hist.hip; models/drift.py
 // holds the definition, the numpy oracle and PSI).  For every row whose stamp equals `stamp`:
 // counts[j][bin_j] += 1 for j < 30, counts[30][amount bucket] += 1 and tail[0] += 1; a row with

@@ -7,7 +7,8 @@ as a script to run, or to paste into a notebook cell by cell (the ``# %%`` marke
 3. compare them on a held-out split (ROC-AUC, PR-AUC);
 4. check that the GBDT's exact 32-byte G32 wire picks the f32 model's leaves;
 5. save versioned safetensors files a running engine hot-swaps (``launch engine --watch-model``);
-6. print the top reasons (exact per-feature Shapley values) of the highest-scoring rows;
+6. print the top reasons (exact per-feature Shapley values) of the highest-scoring rows, for the
+   trained GBDT and for a scikit-learn forest imported with its cover;
 7. with an MI355X visible, score through the HIP kernels and compare with the CPU models.
 
     python examples/model_workbench.py [--csv creditcard.csv] [--rows 200000] [--out models_out]
@@ -106,6 +107,28 @@ def main(argv=None) -> dict:
         report["reasons"]["rows"].append({"row": int(i), "raw_score": float(base_value + row.sum()), "reasons": why})
         print(f"row {int(i)}: log-odds {base_value + row.sum():+.3f} = base {base_value:+.3f} "
               + " ".join(f"{w['feature']} {w['phi']:+.3f}" for w in why) + " ...")
+
+    # %% the same question to a model brought from elsewhere: a scikit-learn forest, imported with its cover
+    try:
+        from sklearn.ensemble import RandomForestClassifier
+    except ImportError:
+        RandomForestClassifier = None
+    if RandomForestClassifier is not None:
+        from ccfd_demo_summit_amd.models.explain_forest import shapley_forest
+        from ccfd_demo_summit_amd.models.sklearn_import import from_sklearn
+        k = min(len(Xtr), 20_000)
+        forest = from_sklearn(RandomForestClassifier(n_estimators=8, max_depth=6, random_state=0).fit(Xtr[:k], ytr[:k]))
+        ftop = np.argsort(-forest.predict_proba(Xte))[:3]
+        if on_gpu:
+            fphi, fbase = DeviceExplainer(forest, device=torch.device(device)).explain(Xte[ftop])
+        else:
+            fphi, fbase = shapley_forest(forest, Xte[ftop])
+        report["forest_reasons"] = {"base_value": float(fbase), "backend": "hip" if on_gpu else "cpu", "rows": []}
+        for i, row in zip(ftop, fphi):
+            why = top_reasons(row, FEATURE_NAMES, 3)
+            report["forest_reasons"]["rows"].append({"row": int(i), "raw_score": float(fbase + row.sum()), "reasons": why})
+            print(f"forest row {int(i)}: class fraction {fbase + row.sum():.3f} = base {fbase:.3f} "
+                  + " ".join(f"{w['feature']} {w['phi']:+.3f}" for w in why) + " ...")
 
     # %% does the holdout still look like the training rows?  (PSI per feature, docs/DRIFT.md)
     from ccfd_demo_summit_amd.models.drift import DriftReference, DriftReport, bin_counts
