@@ -257,7 +257,8 @@ struct G32RowOut {
 };
 
 // What every binned-row kernel does with a lane's scored row: sigmoid of the leaf sum `acc`
-// (stale rows -- meta = bucket | stamp << 8 of another bin table -- are counted, not scored),
+// (stale rows -- meta = bucket | stamp << 8 of another bin table -- are counted, not scored: NaN
+// proba, standard route whatever the rules' default, in neither amount histogram),
 // route by threshold or proba-only rules (kR), proba / route outputs, the workgroup's amount
 // histogram and the wave's counts.  The flag list stays with the caller (emit_flagged and
 // persist_emit_flagged are different protocols).  kProba: `acc` already is the row's
@@ -281,7 +282,8 @@ __device__ __forceinline__ G32RowOut g32_row_epilogue(EpilogueLds& epi, G32Wave&
     if (route) st_g(route + row, (uint8_t)(fr ? 1 : 0));
 #endif
     if (fresh) w.psum += (unsigned)(p * 1e6f + 0.5f);
-    atomicAdd(&epi.hist[(fr ? kNB : 0) + min((int)(meta & 0xffu), kNB - 1)], 1u);
+    // a stale row's bucket byte is as untrusted as its bins (zeroed memory is stale): neither histogram
+    if (fresh) atomicAdd(&epi.hist[(fr ? kNB : 0) + min((int)(meta & 0xffu), kNB - 1)], 1u);
   }
   const unsigned long long m = __ballot(fr);
   w.fraud += __popcll(m);

@@ -332,7 +332,8 @@ def counters_problem(cnt, p, route, X, stale=0):
     if int(cnt[4]) != stale:
         return f"stale {int(cnt[4])} != {stale}"
     b = amount_bucket(X[:, AMOUNT_COL]).astype(np.int64)
-    if not np.array_equal(cnt[8:22], np.bincount(b[route == 0], minlength=14)):
+    # a stale row (NaN proba) is standard-routed but enters neither histogram
+    if not np.array_equal(cnt[8:22], np.bincount(b[(route == 0) & fresh], minlength=14)):
         return f"standard histogram {cnt[8:22].tolist()}"
     if not np.array_equal(cnt[24:38], np.bincount(b[route == 1], minlength=14)):
         return f"fraud histogram {cnt[24:38].tolist()}"

@@ -32,7 +32,8 @@ def _bucket(rows: np.ndarray) -> np.ndarray:
 
 def _check_counters(cnt, p, route, rows, stale=0):
     """tests/test_forest_gpu.py _check_counters, with the amount histogram taken from the rows'
-    bucket byte; a stale row counts as incoming / standard and adds no probability."""
+    bucket byte; a stale row (NaN proba) counts as incoming / standard, adds no probability and
+    enters neither histogram."""
     cnt = cnt.cpu().numpy()
     n = len(p)
     assert cnt[0] == n
@@ -41,7 +42,7 @@ def _check_counters(cnt, p, route, rows, stale=0):
     assert abs(int(cnt[3]) - int(np.nansum(np.round(p.astype(np.float64) * 1e6)))) <= n
     assert cnt[4] == stale
     b = _bucket(rows)
-    np.testing.assert_array_equal(cnt[8:22], np.bincount(b[route == 0], minlength=14))
+    np.testing.assert_array_equal(cnt[8:22], np.bincount(b[(route == 0) & ~np.isnan(p)], minlength=14))
     np.testing.assert_array_equal(cnt[24:38], np.bincount(b[route == 1], minlength=14))
 
 

@@ -8,39 +8,13 @@ import pytest
 from ccfd_demo_summit_amd.config import load_config
 from ccfd_demo_summit_amd.data import generate
 from ccfd_demo_summit_amd.router.rules import MAX_OPS, RuleError, RuleSet, run_device_program
+from tests.helpers.rule_cases import rand_rule as _rand_rule
 
 RULES3 = """
 when amount > 200 and proba >= 0.2 then fraud      # big-ticket, moderately suspicious
 when V17 < -2.5 or abs(V14) > 4 then fraud
 otherwise standard
 """
-
-
-def _rand_expr(rng, depth=0):
-    leaves = ["proba", "amount", "Time", "V1", "V4", "V10", "V12", "V14", "V17", "V28", "FRAUD_THRESHOLD"]
-    r = rng.random()
-    if depth > 2 or r < 0.3:
-        return rng.choice(leaves) if rng.random() < 0.7 else f"{rng.normal() * 3:.4g}"
-    if r < 0.45:
-        return f"({_rand_expr(rng, depth + 1)} {rng.choice(['+', '-', '*', '/'])} {_rand_expr(rng, depth + 1)})"
-    if r < 0.55:
-        f = rng.choice(["abs", "log1p", "min", "max"])
-        if f in ("min", "max"):
-            return f"{f}({_rand_expr(rng, depth + 1)}, {_rand_expr(rng, depth + 1)})"
-        return f"{f}({_rand_expr(rng, depth + 1)})"
-    if r < 0.65:
-        return f"-{_rand_expr(rng, depth + 1)}"
-    return f"{_rand_expr(rng, depth + 1)} {rng.choice(['<', '<=', '>', '>=', '==', '!='])} {_rand_expr(rng, depth + 1)}"
-
-
-def _rand_rule(rng):
-    parts = [_rand_expr(rng) for _ in range(int(rng.integers(1, 3)))]
-    cond = f" {rng.choice(['and', 'or'])} ".join(f"({p}) > 0" if rng.random() < 0.3 else p for p in parts)
-    if rng.random() < 0.2:
-        cond = f"not ({cond})"
-    if rng.random() < 0.15:
-        cond = f"-1 < {rng.choice(['V1', 'V2', 'proba'])} < 0.5"
-    return cond
 
 
 def test_three_rule_set_program_matches_evaluate():
