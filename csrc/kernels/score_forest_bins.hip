@@ -15,14 +15,14 @@
 //     ds_read_b32 -- and extracts byte `feat & 3`.  G20 rows are re-packed to the same byte form,
 //     so both formats share one walk;
 //   * the node table is staged once per workgroup in LDS when it fits kNodeLdsBytes, otherwise
-//     walked from global memory (L2), as in score_forest.hip; a lane walks several trees at once;
+//     walked from global memory (L2), and a lane walks several trees at once: the blob view, the
+//     staging and the walk are score_forest.hip's (forest_core.h), over this file's FrRowBins;
 //   * the scored row goes through the binned kernels' epilogue (g32_row_epilogue: stale stamp
 //     -> NaN + CCFD_CNT_WIRE_STALE, amount bucket from the row, proba-only rules) with the
 //     blob's link applied here.
 //
 // All LDS is one dynamic region -- [wave tiles][epilogue][node table] -- so the node table's
 // 8- and 16-byte accesses are aligned whatever the compiler does with static LDS.
-#include <cstring>
 #include <string>
 
 #include "forest_core.h"
@@ -64,79 +64,18 @@ __device__ __forceinline__ void fb_store_bins(unsigned* col, const unsigned (&b)
   }
 }
 
-// Walk trees t0 .. t0 + U - 1 for the lane's row; returns the leaf sum.  The branch-free step
-// of fr_walk (score_forest.hip): a leaf's child field is its own index and its feature field
-// is 0, so a finished lane stays put and its (ignored) bin read is in bounds.  `(w & 0x1c) << 4`
-// is dword (feat >> 2) * 64 of the column, at most 7 * 64 + 63 of the tile's 512.
-template <int U, bool kLds>
-__device__ __forceinline__ float fb_walk(const int* __restrict__ tree, const uint2* __restrict__ gn, const uint2* ln,
-                                         const unsigned* col, int t0) {
-  FrNode nd[U];
-  int depth = 0;
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int t = t0 + u;
-    const unsigned root = (unsigned)__builtin_amdgcn_readfirstlane(tree[2 * t]);
-    depth = max(depth, __builtin_amdgcn_readfirstlane(tree[2 * t + 1]));
-    nd[u] = fr_node<kLds>(gn, ln, root);
+// The lane's row as the walk reads it (forest_core.h fr_walk): `(w & 0x1c) << 4` is dword
+// (feat >> 2) * 64 of the lane's column, at most 7 * 64 + 63 of the tile's 512 -- a leaf's
+// feature field is 0, so its (ignored) read is in bounds too -- and byte `feat & 3` of it is
+// compared with the node's bin index.
+struct FrRowBins {
+  const unsigned* col;
+  __device__ __forceinline__ unsigned fetch(unsigned w) const { return col[(w & 0x1cu) << 4]; }
+  __device__ __forceinline__ bool right(unsigned x, const FrNode& nd) const {
+    const unsigned bin = (x >> ((nd.w & 3u) * 8u)) & 0xffu;
+    return bin > __float_as_uint(nd.v);
   }
-  for (int s = 0; s < depth; ++s) {
-    unsigned x[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) x[u] = col[(nd[u].w & 0x1cu) << 4];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const unsigned inner = ((nd[u].w >> 5) & 1u) ^ 1u;
-      const unsigned bin = (x[u] >> ((nd[u].w & 3u) * 8u)) & 0xffu;
-      const unsigned gt = bin > __float_as_uint(nd[u].v) ? 1u : 0u;
-      nd[u] = fr_node<kLds>(gn, ln, (nd[u].w >> 8) + (gt & inner));
-    }
-  }
-  float acc = 0.f;
-#pragma unroll
-  for (int u = 0; u < U; ++u) acc += nd[u].v;
-  return acc;
-}
-
-// The trees, kU at a time, then the tail in halving group sizes.
-template <int U, bool kLds>
-__device__ __forceinline__ void fb_tail(const int* __restrict__ tree, const uint2* __restrict__ gn, const uint2* ln,
-                                        const unsigned* col, int T, int& t, float& acc) {
-  if (t + U <= T) { acc += fb_walk<U, kLds>(tree, gn, ln, col, t); t += U; }
-  if constexpr (U > 1) fb_tail<U / 2, kLds>(tree, gn, ln, col, T, t, acc);
-}
-
-template <bool kLds>
-__device__ __forceinline__ float fb_sum(const int* __restrict__ tree, const uint2* __restrict__ gn, const uint2* ln,
-                                        const unsigned* col, int T) {
-  constexpr int kU = kLds ? kFbIlpLds : kFbIlpGlobal;
-  static_assert((kU & (kU - 1)) == 0, "group sizes halve down to 1");
-  float acc = 0.f;
-  int t = 0;
-  for (; t + kU <= T; t += kU) acc += fb_walk<kU, kLds>(tree, gn, ln, col, t);
-  if constexpr (kU > 1) fb_tail<kU / 2, kLds>(tree, gn, ln, col, T, t, acc);
-  return acc;
-}
-
-// The node table into LDS, by the whole workgroup.  16-byte copies: the node section is padded
-// to 16 B, and so is its LDS.  Eight loads are in flight per thread before the first store,
-// where a load-wait-store loop pays one L2 round trip per 4 KB of table; a 65536-row micro-batch
-// is one chunk per wave, so the staging is a visible part of its launch.
-__device__ __forceinline__ void fb_stage_nodes(const uint2* __restrict__ gn, uint2* nl, int n_nodes, int tid) {
-  constexpr int kInFlight = 8;
-  const uint4* s4 = reinterpret_cast<const uint4*>(gn);
-  uint4* d4 = reinterpret_cast<uint4*>(nl);
-  const int n16 = (n_nodes + 1) / 2;
-  for (int i0 = tid; i0 < n16; i0 += 256 * kInFlight) {
-    uint4 v[kInFlight];
-#pragma unroll
-    for (int k = 0; k < kInFlight; ++k)
-      if (i0 + 256 * k < n16) v[k] = ld_g16(s4 + i0 + 256 * k);
-#pragma unroll
-    for (int k = 0; k < kInFlight; ++k)
-      if (i0 + 256 * k < n16) d4[i0 + 256 * k] = v[k];
-  }
-}
+};
 
 // `lds_nodes`: nodes the launch allocated LDS for (0 = none).  T, n_nodes, the link and the
 // stamp come from the blob's own header, so what bounds every read is the blob itself.
@@ -164,16 +103,10 @@ __global__ __launch_bounds__(256) void score_forest_bins_kernel(ccfd_score_args 
   epi_init(epi);
   stamp_start(a, blockIdx.x);
 
-  const char* blob = reinterpret_cast<const char*>(a.blob);
-  const int* __restrict__ hdr = reinterpret_cast<const int*>(blob);
-  const bool sig = (hdr[1] & 1) != 0;
-  const int T = hdr[2];
-  const int n_nodes = hdr[5];
-  const G32Model M{nullptr, nullptr, nullptr, gbb_base(blob), (unsigned)hdr[6]};
-  const int* __restrict__ tree = reinterpret_cast<const int*>(blob + kHeader);
-  const uint2* __restrict__ gn = reinterpret_cast<const uint2*>(blob + kHeader + ((8 * (size_t)T + 15) & ~(size_t)15));
-  const bool resident = n_nodes <= lds_nodes;
-  if (resident) fb_stage_nodes(gn, nl, n_nodes, tid);
+  const FrView m = fr_view(a.blob);
+  const G32Model M{nullptr, nullptr, nullptr, m.base, m.stamp};
+  const bool resident = m.n_nodes <= lds_nodes;
+  if (resident) fr_stage_nodes<256>(m.gn, nl, m.n_nodes, tid);
   __syncthreads();                                              // nodes staged, epi initialised
 
   uint4* tile = xt + wave * 128;
@@ -187,8 +120,10 @@ __global__ __launch_bounds__(256) void score_forest_bins_kernel(ccfd_score_args 
     fb_store_bins(col, b);
     if (c + stride < nchunks) gx_fetch<kG20>(xb, n, c + stride, lane, pre);
 
-    const float z = M.base + (resident ? fb_sum<true>(tree, gn, nl, col, T) : fb_sum<false>(tree, gn, nl, col, T));
-    const float p = sig ? sigmoid(z) : fminf(fmaxf(z, 0.f), 1.f);
+    const FrRowBins bins{col};
+    const float z = M.base + (resident ? fr_sum<kFbIlpLds, true, 1>(m, nl, bins, 0)
+                                       : fr_sum<kFbIlpGlobal, false, 1>(m, nl, bins, 0));
+    const float p = m.sig ? sigmoid(z) : fminf(fmaxf(z, 0.f), 1.f);
     const int row = c * kG32Rows + lane;
     const G32RowOut o = g32_row_epilogue<kR, true>(epi, w, M, meta, p, row, n, a.threshold, a.rules, a.proba, a.route);
     emit_flagged(a, o.fr, row);
@@ -201,43 +136,27 @@ __global__ __launch_bounds__(256) void score_forest_bins_kernel(ccfd_score_args 
   signal_done(a, gridDim.x);
 }
 
-template <bool kR, bool kG20>
-static void launch_fb(const ccfd_score_args& a, hipStream_t s, int grid, int lds_nodes) {
-  const size_t lds = kFbFixedLds + (((size_t)lds_nodes * 8 + 15) & ~(size_t)15);
-  static const bool opted_in = [] {      // dynamic LDS past 64 KB; the launch itself reports a refusal
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&score_forest_bins_kernel<kR, kG20>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, kFbFixedLds + kNodeLdsBytes);
-    (void)hipGetLastError();
-    return true;
-  }();
-  (void)opted_in;
-  hipLaunchKernelGGL((score_forest_bins_kernel<kR, kG20>), dim3(grid), dim3(256), lds, s, a, lds_nodes);
-}
-
 // Grid: one wave per 64-row chunk, capped at 256 x (workgroups per CU) workgroups, grid-stride
-// beyond; as many workgroups per CU as the LDS footprint allows (<= 4: 16 waves / CU).
+// beyond; as many workgroups per CU as the LDS footprint allows.
 int launch_forest_bins(const ccfd_score_args& a, hipStream_t s) {
   if (a.n <= 0) return 0;
-  FrHeader h;
-  if (forest_header(a.blob, h) != 0) { set_error("forest launch: cannot read the blob header"); return -2; }
-  if (std::memcmp(h.magic, "FRB1", 4) != 0) {
-    set_error(std::memcmp(h.magic, "FRS1", 4) == 0
-                  ? "forest launch: an FRS1 blob scores f32 rows, these are G32 / G20 rows (pack with bins=)"
-                  : "forest launch: not an FRB1 blob");
-    return -2;
-  }
-  if (!forest_shape_ok(h, a)) return -2;
-  if (h.stamp < 1 || h.stamp > 255) { set_error("forest launch: FRB1 bin-table stamp outside 1..255"); return -2; }
-  const int lds_nodes = (size_t)h.n_nodes * 8 <= (size_t)kNodeLdsBytes ? h.n_nodes : 0;
-  const int per_cu = min(4, max(1, (160 * 1024) / (kFbFixedLds + lds_nodes * 8)));
+  FrLaunch p;
+  if (const int rc = forest_prepare(a, "FRB1", "FRS1",
+                                    "forest launch: an FRS1 blob scores f32 rows, these are G32 / G20 rows (pack with bins=)",
+                                    kFbFixedLds, p))
+    return rc;
+  if (p.h.stamp < 1 || p.h.stamp > 255) { set_error("forest launch: FRB1 bin-table stamp outside 1..255"); return -2; }
   const int nchunks = (a.n + kG32Rows - 1) / kG32Rows;
-  const int grid = min(256 * per_cu, (nchunks + kG32Waves - 1) / kG32Waves);
-  const bool r = a.rules != nullptr;
-  const bool g20 = (a.flags & CCFD_ARG_WIRE_G20) != 0;
-  if (g20 && r) launch_fb<true, true>(a, s, grid, lds_nodes);
-  else if (g20) launch_fb<false, true>(a, s, grid, lds_nodes);
-  else if (r) launch_fb<true, false>(a, s, grid, lds_nodes);
-  else launch_fb<false, false>(a, s, grid, lds_nodes);
+  const int grid = min(256 * p.per_cu, (nchunks + kG32Waves - 1) / kG32Waves);
+  const size_t lds = kFbFixedLds + (((size_t)p.lds_nodes * 8 + 15) & ~(size_t)15);
+  dispatch_bool(a.rules != nullptr, [&](auto r) {
+    dispatch_bool((a.flags & CCFD_ARG_WIRE_G20) != 0, [&](auto g20) {
+      constexpr auto kernel = &score_forest_bins_kernel<decltype(r)::value, decltype(g20)::value>;
+      static const bool opted_in = (fr_lds_opt_in(kernel, kFbFixedLds + kNodeLdsBytes), true);
+      (void)opted_in;
+      hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, s, a, p.lds_nodes);
+    });
+  });
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

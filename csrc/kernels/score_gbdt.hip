@@ -11,7 +11,8 @@
 //   * each workgroup walks several 64-row chunks with the next chunk prefetched (below);
 //   * the 4 waves split the trees (wave w takes trees w, w+4, ...) over the same 64 rows,
 //     so each SIMD has independent leaf-gather chains in flight; partial sums are reduced
-//     through LDS, then sigmoid + threshold + counters as in the other scorers.
+//     through LDS, then sigmoid + threshold + counters as in the other scorers (the staging
+//     and the row epilogue are gb_rows.h's, shared with score_forest.hip).
 #include <cstdlib>
 #include <cstring>
 
@@ -75,15 +76,7 @@ __global__ __launch_bounds__(256) void score_gbdt_kernel(ccfd_score_args a, int 
     const int row0 = c * kGbRows;
     const int nrows = min(kGbRows, a.n - row0);
     __syncthreads();   // previous chunk's xs / part readers are done
-    if constexpr (kContig) {
-      if (c + 1 < c_end) gb_issue(a.x, row0 + kGbRows, min(kGbRows, a.n - row0 - kGbRows), tid, nxt);
-      gb_store(xs, tid, cur);
-    } else {
-      for (int e = tid; e < kGbRows * kF; e += 256) {
-        const int r = e / kF, f = e % kF;
-        xs[f][r] = (r < nrows) ? a.x[(size_t)(row0 + r) * a.ld + f] : 0.f;
-      }
-    }
+    gb_stage<kContig>(a, xs, tid, row0, nrows, c + 1 < c_end, cur, nxt);
 
     float acc = 0.f;
     for (int c0 = 0; c0 < T; c0 += kChunk) {
@@ -109,23 +102,7 @@ __global__ __launch_bounds__(256) void score_gbdt_kernel(ccfd_score_args a, int 
 
     if (wave == 0) {
       const float z = base + part[0][lane] + part[1][lane] + part[2][lane] + part[3][lane];
-      const float p = sigmoid(z);
-      const bool valid = lane < nrows;
-      // configurable routing rules: row = lane, its features are column xs[*][lane]
-      bool fr;
-      if constexpr (kR) fr = valid && rule_route(a.rules, p, [&](int j) { return xs[j][lane]; });
-      else fr = valid && (p >= a.threshold);
-      const int row = row0 + lane;
-      if (valid) {
-        if (a.proba) st_g(a.proba + row, p);
-        if (a.route) st_g(a.route + row, (uint8_t)(fr ? 1 : 0));
-        atomicAdd(&epi.hist[(fr ? kNB : 0) + amount_bucket(xs[kAmountCol][lane])], 1u);
-      }
-      unsigned long long ps = valid ? (unsigned long long)(p * 1e6f + 0.5f) : 0ull;
-      ps = wave_sum_u64(ps);
-      const unsigned nf = __popcll(__ballot(fr));
-      if (lane == 0) { epi.fraud += nf; epi.rows += nrows; epi.psum_e6 += ps; }
-      emit_flagged(a, fr, row);
+      gb_row_epilogue<kR>(a, epi, xs, sigmoid(z), lane, row0, nrows);
     }
     if constexpr (kContig) cur = nxt;
   }
@@ -376,15 +353,11 @@ static void launch_d(const ccfd_score_args& a, hipStream_t s, bool contig) {
   const int cpw = gbdt_chunks_per_wg(nchunks);
   const int grid = (nchunks + cpw - 1) / cpw;
   const size_t lds = (size_t)min(a.gbdt_trees, kLeafLds / L) * L * sizeof(float);
-  const bool r = a.rules != nullptr;    // routing rules: separate instantiation (register budget)
-  if (contig && r)
-    hipLaunchKernelGGL((score_gbdt_kernel<D, true, true>), dim3(grid), dim3(256), lds, s, a, cpw);
-  else if (contig)
-    hipLaunchKernelGGL((score_gbdt_kernel<D, true, false>), dim3(grid), dim3(256), lds, s, a, cpw);
-  else if (r)
-    hipLaunchKernelGGL((score_gbdt_kernel<D, false, true>), dim3(grid), dim3(256), lds, s, a, cpw);
-  else
-    hipLaunchKernelGGL((score_gbdt_kernel<D, false, false>), dim3(grid), dim3(256), lds, s, a, cpw);
+  dispatch_bool(contig, [&](auto c) {
+    dispatch_bool(a.rules != nullptr, [&](auto r) {    // routing rules: separate instantiation (register budget)
+      hipLaunchKernelGGL((score_gbdt_kernel<D, decltype(c)::value, decltype(r)::value>), dim3(grid), dim3(256), lds, s, a, cpw);
+    });
+  });
 }
 
 int launch_gbdt(const ccfd_score_args& a, hipStream_t s) {

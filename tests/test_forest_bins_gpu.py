@@ -7,69 +7,15 @@ import numpy as np
 import pytest
 import torch
 
-from ccfd_demo_summit_amd.contracts.transaction import decode_g20_bins
 from ccfd_demo_summit_amd.data import generate
 from ccfd_demo_summit_amd.models import TreeEnsemble, build_model
 from ccfd_demo_summit_amd.models.forest import LDS_NODE_BYTES, NODE_BYTES
+from tests.helpers.forest_cases import _chain, _concat, proba_bound
+from tests.helpers.forest_cases import check_counters_bins as _check_counters
 
 pytestmark = pytest.mark.gpu
 
 N_DATA = 70001
-
-
-def proba_bound(m: TreeEnsemble) -> float:
-    """fp32 bound on a probability (tests/test_forest_gpu.py, derived in tests/test_forest_cpu.py):
-    T float32 roundings of magnitude <= |base| + sum_t max|leaf_t| in the sum, times the
-    sigmoid's slope 1/4.  The binned walk selects the f32 walk's leaves exactly, so the bound
-    is the f32 kernel's."""
-    return 0.25 * m.n_trees * 2.0 ** -23 * (abs(m.base) + m.leaf_abs_max().sum()) + 1e-6
-
-
-def _bucket(rows: np.ndarray) -> np.ndarray:
-    """The amount bucket a binned row carries (G32: byte 30; G20: bits 150..153)."""
-    return (rows if rows.shape[1] == 32 else decode_g20_bins(rows))[:, 30]
-
-
-def _check_counters(cnt, p, route, rows, stale=0):
-    """tests/test_forest_gpu.py _check_counters, with the amount histogram taken from the rows'
-    bucket byte; a stale row (NaN proba) counts as incoming / standard, adds no probability and
-    enters neither histogram."""
-    cnt = cnt.cpu().numpy()
-    n = len(p)
-    assert cnt[0] == n
-    assert cnt[1] == route.sum()
-    assert cnt[2] == n - route.sum()
-    assert abs(int(cnt[3]) - int(np.nansum(np.round(p.astype(np.float64) * 1e6)))) <= n
-    assert cnt[4] == stale
-    b = _bucket(rows)
-    np.testing.assert_array_equal(cnt[8:22], np.bincount(b[(route == 0) & ~np.isnan(p)], minlength=14))
-    np.testing.assert_array_equal(cnt[24:38], np.bincount(b[route == 1], minlength=14))
-
-
-def _concat(parts):
-    feat, value, child, leaf, root, off = [], [], [], [], [], 0
-    for m in parts:
-        feat.append(m.feat); value.append(m.value); leaf.append(m.leaf)
-        child.append(m.child + off); root.append(m.root + off)
-        off += m.n_nodes
-    return TreeEnsemble(np.concatenate(feat), np.concatenate(value), np.concatenate(child), np.concatenate(leaf),
-                        np.concatenate(root), parts[0].base, parts[0].link)
-
-
-def _chain(depth, X, seed):
-    """One tree of depth ``depth``: every right child splits again, every left child is a
-    leaf; thresholds at the 15 % quantile so that rows spread over the whole chain."""
-    rng = np.random.default_rng(seed)
-    n = depth
-    feat = np.array([1] + [0, 1] * (n - 1) + [0, 0])
-    leaf = np.array([False] + [True, False] * (n - 1) + [True, True])
-    child = np.array([1] + [0, 0] * (n - 1) + [0, 0])
-    child[2:2 * n - 1:2] = 3 + 2 * np.arange(n - 1)
-    inner = np.flatnonzero(~leaf)
-    feat[inner] = rng.integers(0, 30, inner.size)
-    value = (rng.standard_normal(feat.size) * 0.3).astype(np.float32)
-    value[inner] = [np.quantile(X[:, f], 0.15) for f in feat[inner]]
-    return TreeEnsemble(feat, value, child, leaf, [0])
 
 
 @pytest.fixture(scope="module")
@@ -99,7 +45,7 @@ def ensembles(data):
         "t1": TreeEnsemble.random_init(1, 6, 0.2, 1, X),
         "t3": TreeEnsemble.random_init(3, 5, 0.2, 2, X),          # tail groups of 2 and 1
         "t5": TreeEnsemble.random_init(5, 7, 0.25, 3, X),         # tail groups of 4 and 1
-        "t21": TreeEnsemble.random_init(21, 6, 0.2, 9, X),        # two full groups of 8, then 4 and 1
+        "t21": TreeEnsemble.random_init(21, 6, 0.2, 9, X),        # one full group of 16, then 4 and 1
         "leaf_only_among": _concat([TreeEnsemble.random_init(2, 4, 0.2, 4, X), one_leaf,
                                     TreeEnsemble.random_init(3, 4, 0.2, 5, X)]),
         "stumps": TreeEnsemble.random_init(9, 1, 0.0, 6, X),

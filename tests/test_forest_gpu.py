@@ -6,64 +6,13 @@ import numpy as np
 import pytest
 import torch
 
-from ccfd_demo_summit_amd.contracts.metric_names import AMOUNT_BUCKETS
 from ccfd_demo_summit_amd.data import generate
 from ccfd_demo_summit_amd.models import TreeEnsemble, build_model
 from ccfd_demo_summit_amd.models.forest import LDS_NODE_BYTES, NODE_BYTES
+from tests.helpers.forest_cases import _chain, _concat, proba_bound
+from tests.helpers.forest_cases import check_counters_f32 as _check_counters
 
 pytestmark = pytest.mark.gpu
-
-
-def _counters_ref(p, route, X):
-    amt = X[:, 29]
-    b = np.searchsorted(np.asarray(AMOUNT_BUCKETS, np.float32), amt, side="left")
-    hist_std = np.bincount(b[route == 0], minlength=14)
-    hist_fr = np.bincount(b[route == 1], minlength=14)
-    return hist_std, hist_fr
-
-
-def _check_counters(cnt, p, route, X):
-    cnt = cnt.cpu().numpy()
-    n = len(p)
-    assert cnt[0] == n
-    assert cnt[1] == route.sum()
-    assert cnt[2] == n - route.sum()
-    assert abs(int(cnt[3]) - int(np.round(p.astype(np.float64) * 1e6).sum())) <= n
-    hs, hf = _counters_ref(p, route, X)
-    np.testing.assert_array_equal(cnt[8:22], hs)
-    np.testing.assert_array_equal(cnt[24:38], hf)
-
-
-def proba_bound(m: TreeEnsemble) -> float:
-    """fp32 bound on a probability (see tests/test_forest_cpu.py): T float32 roundings of
-    magnitude <= |base| + sum_t max|leaf_t| in the sum, times the sigmoid's slope 1/4."""
-    return 0.25 * m.n_trees * 2.0 ** -23 * (abs(m.base) + m.leaf_abs_max().sum()) + 1e-6
-
-
-def _concat(parts):
-    feat, value, child, leaf, root, off = [], [], [], [], [], 0
-    for m in parts:
-        feat.append(m.feat); value.append(m.value); leaf.append(m.leaf)
-        child.append(m.child + off); root.append(m.root + off)
-        off += m.n_nodes
-    return TreeEnsemble(np.concatenate(feat), np.concatenate(value), np.concatenate(child), np.concatenate(leaf),
-                        np.concatenate(root), parts[0].base, parts[0].link)
-
-
-def _chain(depth, X, seed):
-    """One tree of depth ``depth``: every right child splits again, every left child is a
-    leaf; thresholds at the 15 % quantile so that rows spread over the whole chain."""
-    rng = np.random.default_rng(seed)
-    n = depth
-    feat = np.array([1] + [0, 1] * (n - 1) + [0, 0])
-    leaf = np.array([False] + [True, False] * (n - 1) + [True, True])
-    child = np.array([1] + [0, 0] * (n - 1) + [0, 0])
-    child[2:2 * n - 1:2] = 3 + 2 * np.arange(n - 1)
-    inner = np.flatnonzero(~leaf)
-    feat[inner] = rng.integers(0, 30, inner.size)
-    value = (rng.standard_normal(feat.size) * 0.3).astype(np.float32)
-    value[inner] = [np.quantile(X[:, f], 0.15) for f in feat[inner]]
-    return TreeEnsemble(feat, value, child, leaf, [0])
 
 
 @pytest.fixture(scope="module")
