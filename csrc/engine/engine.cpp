@@ -21,11 +21,9 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <deque>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -35,11 +33,12 @@
 
 #include <sys/prctl.h>
 
-#if defined(__x86_64__)
-#include <immintrin.h>
-#endif
-
 #include "../include/ccfd_abi.h"
+#include "arrival_log.h"
+#include "completion_stamper.h"
+#include "lat_stats.h"
+#include "persist_plan.h"
+#include "record_ring.h"
 #include "spsc_ring.h"
 
 namespace ccfd {
@@ -51,17 +50,14 @@ int item_trace_dump(const char* path);     // score_gbdt_g32_persist.hip, experi
 
 namespace {
 
+using ccfd::cpu_relax;
+using ccfd::now_ns;
 using ccfd::set_error;
 
 // persistent engines alive in this process, per device: hardware queues belong to a device,
 // so the GPU_MAX_HW_QUEUES bound is per device, not per process
 constexpr int kMaxDevices = 64;
 std::atomic<int> g_persist_engines[kMaxDevices];
-
-inline int64_t now_ns() {
-  return std::chrono::duration_cast<std::chrono::nanoseconds>(
-             std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 
 #define HIPCHK(expr)                                                          \
   do {                                                                        \
@@ -71,6 +67,28 @@ inline int64_t now_ns() {
       return -4;                                                              \
     }                                                                         \
   } while (0)
+
+constexpr unsigned kMappedCoherent = hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent;
+
+// pinned host memory the device can address (zeroed if asked): the host pointer and its device alias
+template <class H, class D>
+int alloc_mapped(H** host, D** dev, size_t bytes, bool zero, unsigned flags = kMappedCoherent) {
+  void* p = nullptr;
+  HIPCHK(hipHostMalloc(&p, bytes, flags));
+  if (zero) std::memset(p, 0, bytes);
+  *host = static_cast<H*>(p);
+  void* d = nullptr;
+  HIPCHK(hipHostGetDevicePointer(&d, p, 0));
+  *dev = static_cast<D*>(d);
+  return 0;
+}
+
+// adds the time from t0 to the end of a submit call to the host time counter
+struct SubmitTimer {
+  uint64_t& acc;
+  int64_t t0;
+  ~SubmitTimer() { acc += now_ns() - t0; }
+};
 
 struct Partition {
   const float* feats = nullptr;      // host pointer
@@ -83,24 +101,7 @@ struct Partition {
   // ring (streaming) mode: SPSC ring of n rows; producer = ingest thread, consumer = run()
   bool ring = false;
   ccfd::RowRing rr;                  // SPSC row ring (csrc/engine/spsc_ring.h)
-  std::mutex arr_mu;
-  struct Arrival { int64_t head, t, origin; };       // head after commit, commit time, producer send time
-  std::deque<Arrival> arrivals;
-
-  Arrival arrival_of(int64_t row) {   // commit (and origin) time of `row`
-    std::lock_guard<std::mutex> lk(arr_mu);
-    // heads increase monotonically: binary search (a JSON feed commits one entry per message,
-    // so tens of thousands of entries are in flight and a linear scan held arr_mu -- and the
-    // ingest thread's next commit -- for tens of microseconds)
-    auto it = std::upper_bound(arrivals.begin(), arrivals.end(), row,
-                               [](int64_t r, const Arrival& a) { return r < a.head; });
-    if (it != arrivals.end()) return *it;
-    return arrivals.empty() ? Arrival{0, 0, 0} : arrivals.back();
-  }
-  void forget_before(int64_t row) {
-    std::lock_guard<std::mutex> lk(arr_mu);
-    while (!arrivals.empty() && arrivals.front().head <= row) arrivals.pop_front();
-  }
+  ccfd::ArrivalLog arrivals;         // commit / send time of the ring's rows (csrc/engine/arrival_log.h)
 };
 
 struct Slot {
@@ -132,12 +133,6 @@ struct Slot {
   int64_t seq_no = 0;
 };
 
-inline void cpu_relax() {
-#if defined(__x86_64__)
-  _mm_pause();
-#endif
-}
-
 class Engine {
  public:
   ccfd_engine_config cfg{};
@@ -148,30 +143,14 @@ class Engine {
   uint64_t seq = 0;
   int next_part = 0;
   int epoch = 0;
-  // flagged hand-off ring (producer: pump thread; consumer: drain, any thread)
-  std::vector<ccfd_flagged> ring;
-  uint64_t ring_head = 0, ring_tail = 0;
-  std::mutex ring_mu;
-  uint64_t dropped = 0;              // must stay 0: complete() reserves room first (lossless)
+  // flagged hand-off ring (producer: pump thread; consumer: drain, any thread); its dropped
+  // count must stay 0: complete() reserves room first (lossless)
+  ccfd::RecordRing<ccfd_flagged> flagged;
   uint64_t flag_full_events = 0;     // completions deferred because the ring was full
   // opt-in scored-record ring (every row; ccfd_engine_scored_enable), same producer/consumer
-  std::vector<ccfd_scored> sring;
-  uint64_t s_head = 0, s_tail = 0, s_dropped = 0;
-  std::mutex s_mu;
+  ccfd::RecordRing<ccfd_scored> scored;
   std::atomic<bool> scored_on{false};
-  // per-batch latency: O(1) memory however long the engine runs (a long-lived service
-  // scores ~2e5 batches/s): count/sum/max, a 0.25-us linear histogram up to 4 ms for the
-  // reported quantiles, and the 4-buckets-per-octave log histogram merged over ranks (X3)
-  static constexpr int kFineBuckets = 16384;
-  static constexpr double kFineUs = 0.25;
-  uint64_t lat_n = 0, lat_over = 0;
-  double lat_sum_us = 0.0, lat_max_us = 0.0;
-  std::vector<uint64_t> lat_fine = std::vector<uint64_t>(kFineBuckets, 0u);   // u64: never wraps
-  uint64_t lat_hist[256] = {};
-  uint64_t t_submit_ns = 0, t_wait_ns = 0, t_complete_ns = 0;
-  uint64_t dev_batches = 0, dev_exec_ns = 0, dev_hist[256] = {};
-  uint64_t lat_hist_rows[256] = {}, dev_hist_rows[256] = {};   // row-weighted (Seldon histograms)
-  uint64_t origin_batches = 0, origin_hist[256] = {}, origin_hist_rows[256] = {};   // produce -> scored
+  ccfd::LatencyStats lat;            // per-batch latency and host time counters (lat_stats.h)
   // last completed transaction (model "last request" gauges)
   uint64_t last_seq = 0, last_tx_id = 0;
   float last_proba = 0.f, last_amount = 0.f;
@@ -183,70 +162,15 @@ class Engine {
   std::atomic<bool> trace_on{false};       // fast check on the completion path
   double wall_ns_per_tick = 0.0;   // device wall clock (s_memrealtime) period
   unsigned long long done_counter = 0;
-
-  // Completion stamper (CCFD_COMPLETION_THREAD, default on): a host thread that watches the
-  // kernel-published completion records of the in-flight micro-batches and stamps the host
-  // time each one lands, so a batch's latency ends when its results are in host memory, not
-  // when the pump thread next looks (between pump() calls the caller runs the router
-  // hand-off and the X2 tick: without the stamper those milliseconds were charged to every
-  // batch that completed meanwhile -- the p99 tail).  One packed word per slot: the low 16
-  // bits of the awaited sequence number << 48 | ns since the engine started (48 bits), so a
-  // stamp can never be attributed to another use of the slot.
-  bool stamper_on = false;
-  int64_t stamp_base_ns = 0;
-  std::unique_ptr<std::atomic<unsigned long long>[]> st_armed;            // awaited seq (0 = idle)
-  std::unique_ptr<std::atomic<const volatile unsigned long long*>[]> st_ptr;
-  std::unique_ptr<std::atomic<uint64_t>[]> st_word;                       // tag << 48 | t
-  std::thread stamper;
-  std::atomic<bool> stamper_stop{false};
-
-  static constexpr uint64_t kStampMask = (1ull << 48) - 1;
-
-  void stamper_loop() {
-    prctl(PR_SET_TIMERSLACK, 1000UL, 0, 0, 0);
-    const int D = (int)slots.size();
-    while (!stamper_stop.load(std::memory_order_relaxed)) {
-      bool any = false;
-      for (int i = 0; i < D; ++i) {
-        const unsigned long long e = st_armed[i].load(std::memory_order_acquire);
-        if (!e) continue;
-        any = true;
-        const uint64_t tag = (uint64_t)(e & 0xffffull) << 48;
-        if ((st_word[i].load(std::memory_order_relaxed) & ~kStampMask) == tag) continue;   // stamped
-        const volatile unsigned long long* p = st_ptr[i].load(std::memory_order_relaxed);
-        if (p && p[0] == e) {
-          st_word[i].store(tag | ((uint64_t)(now_ns() - stamp_base_ns) & kStampMask), std::memory_order_release);
-          stamps_written.fetch_add(1, std::memory_order_relaxed);
-        }
-      }
-      stamper_iters.fetch_add(1, std::memory_order_relaxed);
-      if (any) cpu_relax();
-      else std::this_thread::sleep_for(std::chrono::microseconds(2));
-    }
-  }
+  ccfd::CompletionStamper stamper;   // CCFD_COMPLETION_THREAD, default on (completion_stamper.h)
 
   // after s.done_ptr / s.expect are set for a kernel-published completion
-  void arm(Slot& s) {
-    if (!stamper_on) return;
-    const size_t i = (size_t)(&s - slots.data());
-    st_ptr[i].store(s.done_ptr, std::memory_order_relaxed);
-    st_armed[i].store(s.expect, std::memory_order_release);
-  }
+  void arm(Slot& s) { stamper.arm((size_t)(&s - slots.data()), s.done_ptr, s.expect); }
 
   // host time the completion record of `s` landed (stamper), else `fallback`
-  uint64_t stamp_used = 0, stamp_missed = 0, stamp_rejected = 0;   // CCFD_STAMPER_DEBUG report
-  std::atomic<uint64_t> stamps_written{0}, stamper_iters{0};
-
   int64_t landed_ns(Slot& s, int64_t fallback) {
-    if (!stamper_on || !s.use_flag) return fallback;
-    const size_t i = (size_t)(&s - slots.data());
-    const uint64_t w = st_word[i].load(std::memory_order_acquire);
-    st_armed[i].store(0, std::memory_order_relaxed);
-    if ((w >> 48) != (s.expect & 0xffffull)) { ++stamp_missed; return fallback; }
-    const int64_t t = stamp_base_ns + (int64_t)(w & kStampMask);
-    if (t <= fallback && t >= s.t_submit) { ++stamp_used; return t; }
-    ++stamp_rejected;
-    return fallback;
+    if (!s.use_flag) return fallback;
+    return stamper.landed_ns((size_t)(&s - slots.data()), s.expect, s.t_submit, fallback);
   }
 
   int init(const ccfd_engine_config& c) {
@@ -303,36 +227,21 @@ class Engine {
         HIPCHK(hipMalloc(&s.d_proba, B * sizeof(float)));
         HIPCHK(hipMalloc(&s.d_route, B));
       }
-      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s.h_proba), B * sizeof(float), out_flags));
-      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s.h_route), B, out_flags));
-      HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&s.h_proba_dev), s.h_proba, 0));
-      HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&s.h_route_dev), s.h_route, 0));
+      if (int rc = alloc_mapped(&s.h_proba, &s.h_proba_dev, B * sizeof(float), false, out_flags)) return rc;
+      if (int rc = alloc_mapped(&s.h_route, &s.h_route_dev, B, false, out_flags)) return rc;
       HIPCHK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
       HIPCHK(hipMalloc(reinterpret_cast<void**>(&s.d_ctl), 4 * sizeof(unsigned int)));
       HIPCHK(hipMemsetAsync(s.d_ctl, 0, 4 * sizeof(unsigned int), streams[0]));
-      HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&s.h_flag), B * sizeof(unsigned int), out_flags));
-      HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&s.h_flag_dev), s.h_flag, 0));
-      void* hd = nullptr;
-      HIPCHK(hipHostMalloc(&hd, 64, hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent));
-      std::memset(hd, 0, 64);
-      s.h_done = static_cast<volatile unsigned long long*>(hd);
-      HIPCHK(hipHostGetDevicePointer(reinterpret_cast<void**>(&s.h_done_dev), hd, 0));
+      if (int rc = alloc_mapped(&s.h_flag, &s.h_flag_dev, B * sizeof(unsigned int), false, out_flags)) return rc;
+      if (int rc = alloc_mapped(&s.h_done, &s.h_done_dev, 64, true)) return rc;
     }
     // never hipDeviceSynchronize here: another engine's persistent kernel may be resident
     HIPCHK(hipStreamSynchronize(streams[0]));
     // one micro-batch must always fit (a batch is handed off whole or not at all)
-    ring.resize(std::max({1024, cfg.flag_capacity, cfg.max_batch}));
-    stamper_on = true;
+    flagged.reset((size_t)std::max({1024, cfg.flag_capacity, cfg.max_batch}));
+    bool stamper_on = true;
     if (const char* e = std::getenv("CCFD_COMPLETION_THREAD")) stamper_on = std::atoi(e) != 0;
-    if (stamper_on) {
-      const size_t D = slots.size();
-      st_armed.reset(new std::atomic<unsigned long long>[D]);
-      st_ptr.reset(new std::atomic<const volatile unsigned long long*>[D]);
-      st_word.reset(new std::atomic<uint64_t>[D]);
-      for (size_t i = 0; i < D; ++i) { st_armed[i] = 0; st_ptr[i] = nullptr; st_word[i] = 0; }
-      stamp_base_ns = now_ns();
-      stamper = std::thread([this] { stamper_loop(); });
-    }
+    if (stamper_on) stamper.start(slots.size());
     if (cfg.exec_mode == 1) return persist_init();
     return 0;
   }
@@ -356,13 +265,13 @@ class Engine {
   // flight (CCFD_IDLE_FLUSH_US; < 0 = off: partial batches wait for the flush deadline)
   int64_t idle_flush_ns = 20'000;
   ccfd_persist_ctl* pctl = nullptr;       // host (coherent pinned)
+  ccfd_persist_ctl* pctl_dev = nullptr;    // ... and its device alias
   ccfd_persist_desc* pdesc = nullptr;      // host (coherent pinned)
+  const ccfd_persist_desc* pdesc_dev = nullptr;
   ccfd_persist_dev* pdev = nullptr;        // device
   hipStream_t pstream = nullptr;
   bool prunning = false;
-  int persist_C = 0;
-  int persist_tpw = 1;
-  bool persist_pipe = false;
+  ccfd::PersistPlan plan;                  // item size, items per batch, grid (persist_plan.h)
   const void* shadow_blob = nullptr;       // challenger (MLP / GBDT) scored beside cfg.blob (set_shadow)
   int64_t completed_upto = 0;              // batches completed in order (seq count)
   std::vector<int64_t> flip_seq;           // seq at each epoch flip
@@ -393,58 +302,12 @@ class Engine {
       }
       persist_counted = true;
     }
-    void* p = nullptr;
-    HIPCHK(hipHostMalloc(&p, sizeof(ccfd_persist_ctl), hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent));
-    std::memset(p, 0, sizeof(ccfd_persist_ctl));
-    pctl = static_cast<ccfd_persist_ctl*>(p);
-    HIPCHK(hipHostMalloc(&p, sizeof(ccfd_persist_desc) * cfg.depth,
-                         hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent));
-    std::memset(p, 0, sizeof(ccfd_persist_desc) * cfg.depth);
-    pdesc = static_cast<ccfd_persist_desc*>(p);
-    // work-item size: 64 rows (one 16-row tile per wave) by default; CCFD_PERSIST_ITEM_ROWS
-    // = 128/256 gives each wave 2/4 tiles with a one-tile prefetch (fewer claims per batch)
-    // GBDT on G32 rows: items of 4 waves x 64-row chunks (256 / 512 / 1024 rows, default 512)
-    // W64 rows on 64 workgroups, every tile of an item in flight at once (score_persist.hip):
-    // MLP 512-row items -- 8.63e8 tx/s at p50 53 us and depth 12 vs 8.56e8 at 72 us for
-    // 256-row items on 128 workgroups at depth 16; LR 256-row items (8.47e8 at 56 us; 512:
-    // 7.3e8) -- profiles/r2/persist_full_item/
-    const bool w64 = (wire_flag & CCFD_ARG_WIRE_W64) != 0;
-    // G32 ensembles far beyond BASELINE's 100 x 6 (> 1200 tree levels a row) are VALU-bound:
-    // 256-row items on 512 workgroups spread them over more waves (700 x 6 at depth 6:
-    // 1.01e9 tx/s vs 7.3e8 with 512-row items on 256, profiles/r2/g32_large_ensembles/)
-    const bool big_trees = g32 && cfg.gbdt_trees * cfg.gbdt_depth > 1200;
-    int item_rows = big_trees ? 256 : (g32 || (w64 && cfg.model == CCFD_MODEL_MLP)) ? 512 : CCFD_PERSIST_ITEM_ROWS;
-    if (const char* e = std::getenv("CCFD_PERSIST_ITEM_ROWS")) {
-      const int v = std::atoi(e);
-      if (v == 256 || v == 512 || v == 1024 || (!g32 && (v == 64 || v == 128))) item_rows = v;
-    }
-    persist_tpw = g32 ? item_rows / 256 : item_rows / 64;
-    // Pipelined static items (MLP on W64 rows, score_persist.hip persist_pipe_kernel): a
-    // micro-batch spread over 32 workgroups / CUs, the next item's rows fetched while the
-    // current one is scored -- 19 us unloaded latency vs 29 us for claimed 512-row items,
-    // better up to ~4 batches in flight, capped near 6.5e8 tx/s beyond
-    // (profiles/r3/latency/).  cfg.persist_items: 2 = pipelined, 1 = claimed, 0 = env
-    // CCFD_PERSIST_PIPE (default claimed).  CCFD_PERSIST_ITEM_ROWS = 64 / 128 (default 128).
-    persist_pipe = false;
-    // GBDT on G32 / G20 rows: the same pipelined static items, 512-row items, leaves in LDS
-    // (score_gbdt_g32_persist.hip persist_gbdt_pipe_kernel)
-    const bool g32_pipe_ok = g32 && !big_trees && ((long)cfg.gbdt_trees << cfg.gbdt_depth) <= 16384;   // kG32LeafLds
-    if ((w64 && cfg.model == CCFD_MODEL_MLP) || g32_pipe_ok) {
-      if (cfg.persist_items == 2) persist_pipe = true;
-      else if (cfg.persist_items == 0)
-        if (const char* e = std::getenv("CCFD_PERSIST_PIPE")) persist_pipe = std::atoi(e) != 0;
-    }
-    if (persist_pipe && g32) {
-      item_rows = 512;
-      persist_tpw = 2;
-    } else if (persist_pipe) {
-      item_rows = 128;
-      if (const char* e = std::getenv("CCFD_PERSIST_ITEM_ROWS")) if (std::atoi(e) == 64) item_rows = 64;
-      persist_tpw = item_rows / 64;
-    }
-    const int C = (cfg.max_batch + item_rows - 1) / item_rows;
+    if (int rc = alloc_mapped(&pctl, &pctl_dev, sizeof(ccfd_persist_ctl), true)) return rc;
+    if (int rc = alloc_mapped(&pdesc, &pdesc_dev, sizeof(ccfd_persist_desc) * cfg.depth, true)) return rc;
+    plan = ccfd::persist_plan(cfg.model, cfg.wire, cfg.gbdt_trees, cfg.gbdt_depth, cfg.max_batch, cfg.persist_items,
+                              cfg.persist_grid, std::getenv("CCFD_PERSIST_ITEM_ROWS"), std::getenv("CCFD_PERSIST_PIPE"));
     ccfd_persist_dev init{};
-    for (int i = 0; i < CCFD_PERSIST_MAX_RING; ++i) init.remaining[i] = (unsigned)C;
+    for (int i = 0; i < CCFD_PERSIST_MAX_RING; ++i) init.remaining[i] = (unsigned)plan.items_per_batch;
     HIPCHK(hipMalloc(reinterpret_cast<void**>(&pdev), sizeof(ccfd_persist_dev)));
     HIPCHK(hipMemcpy(pdev, &init, sizeof(init), hipMemcpyHostToDevice));
     // The persistent kernel never ends, and the HIP runtime multiplexes streams onto
@@ -458,7 +321,6 @@ class Engine {
       HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
       HIPCHK(hipStreamCreateWithPriority(&pstream, hipStreamNonBlocking, least));
     }
-    persist_C = C;
     persistent = true;
     return 0;
   }
@@ -467,25 +329,22 @@ class Engine {
   // re-based on the host's `posted` count: every posted batch has completed (halt drains).
   int persist_launch() {
     ccfd_persist_dev init{};
-    init.work_next = (unsigned long long)pctl->posted * (unsigned long long)persist_C;
+    init.work_next = (unsigned long long)pctl->posted * (unsigned long long)plan.items_per_batch;
     init.posted = pctl->posted;
     init.stop = 0;
-    for (int i = 0; i < CCFD_PERSIST_MAX_RING; ++i) init.remaining[i] = (unsigned)persist_C;
+    for (int i = 0; i < CCFD_PERSIST_MAX_RING; ++i) init.remaining[i] = (unsigned)plan.items_per_batch;
     HIPCHK(hipMemcpyAsync(pdev, &init, sizeof(init), hipMemcpyHostToDevice, pstream));
     HIPCHK(hipStreamSynchronize(pstream));
     __atomic_store_n(&pctl->stop, 0ull, __ATOMIC_RELEASE);
     ccfd_persist_args a{};
-    void* d = nullptr;
-    HIPCHK(hipHostGetDevicePointer(&d, pctl, 0));
-    a.ctl = static_cast<ccfd_persist_ctl*>(d);
-    HIPCHK(hipHostGetDevicePointer(&d, pdesc, 0));
-    a.desc = static_cast<const ccfd_persist_desc*>(d);
+    a.ctl = pctl_dev;
+    a.desc = pdesc_dev;
     a.dev = pdev;
     a.ring = cfg.depth;
-    a.items_per_batch = persist_C;
-    a.tiles_per_wave = persist_tpw;
+    a.items_per_batch = plan.items_per_batch;
+    a.tiles_per_wave = plan.tiles_per_wave;
     a.flags = (coherent_out ? CCFD_ARG_FENCE_COHERENT : CCFD_ARG_FENCE_SYS) | wire_flag |
-              (persist_pipe ? CCFD_ARG_PIPE_ITEMS : 0);
+              (plan.pipe ? CCFD_ARG_PIPE_ITEMS : 0);
     a.model = cfg.model;
     a.threshold = cfg.threshold;
     a.rules = cfg.rules;
@@ -494,83 +353,70 @@ class Engine {
     a.counters[1] = cfg.counters[1];
     a.gbdt_trees = cfg.gbdt_trees;
     a.gbdt_depth = cfg.gbdt_depth;
-    // resident workgroups (+ the doorbell): 128 for GBDT G32 (1.68e9 tx/s vs 1.62e9 at 256 and
-    // 1.34e9 at 768, profiles/r2/gbdt_g32_persist_sweep.jsonl) and f32 rows; 64 for W64 rows
-    // (their 512-row items keep 32 KB per workgroup in flight)
-    // G32 ensembles well beyond BASELINE's 100 x 6 are VALU-bound, not PCIe-bound: two
-    // workgroups per CU (see persist_init; 700 x 6: 3.8e8 tx/s at 128, 7.3e8 at 256 and
-    // 1.01e9 at 512 with 256-row items, profiles/r2/g32_large_ensembles/)
-    // G20 rows carry 1.6x the rows of G32 per PCIe byte, so more resident workgroups keep
-    // up: 216 (2.56-2.57e9 tx/s at p50 91 us, depth 4, 512-row items) vs 2.52e9 at 192,
-    // 2.53e9 at 240 and 2.45e9 at 249 (profiles/r5/pass_w/; r2: 2.18e9 at 128, g20/sweep.txt)
-    const bool big_trees = (wire_flag & CCFD_ARG_WIRE_G32) && cfg.gbdt_trees * cfg.gbdt_depth > 1200;
-    const int grid = cfg.persist_grid > 0 ? cfg.persist_grid
-                     : persist_pipe ? CCFD_PERSIST_GRID
-                     : (wire_flag & CCFD_ARG_WIRE_W64) ? CCFD_PERSIST_GRID_W64
-                     : big_trees ? 4 * CCFD_PERSIST_GRID
-                     : (wire_flag & CCFD_ARG_WIRE_G20) ? CCFD_PERSIST_GRID_G20 : CCFD_PERSIST_GRID;
     int rc;
     if (shadow_blob) {
       ccfd_persist_shadow_args sa{};
       sa.base = a;
       sa.shadow_blob = shadow_blob;
-      rc = ccfd_persist_launch_shadow(&sa, grid, pstream);
+      rc = ccfd_persist_launch_shadow(&sa, plan.grid, pstream);
     } else {
-      rc = ccfd_persist_launch(&a, grid, pstream);
+      rc = ccfd_persist_launch(&a, plan.grid, pstream);
     }
     if (rc) { set_error("persistent kernel launch failed"); return rc; }
     prunning = true;
     return 0;
   }
 
+  // Raise the stop word every waiting workgroup polls and wait for the kernel's stream to go
+  // idle, looking every `sleep_us`; false = still resident after `timeout_ns`.  Touches only
+  // the host control record and queries the stream (the watchdog calls it without the lock).
+  bool persist_stop_wait(int64_t timeout_ns, int sleep_us, hipError_t* q) {
+    __atomic_store_n(&pctl->stop, 1ull, __ATOMIC_RELEASE);
+    const int64_t t0 = now_ns();
+    while ((*q = hipStreamQuery(pstream)) == hipErrorNotReady) {
+      if (now_ns() - t0 > timeout_ns) return false;
+      std::this_thread::sleep_for(std::chrono::microseconds(sleep_us));
+    }
+    return true;
+  }
+
   // Stop the persistent kernel: every posted batch must be complete (callers drain first);
   // all workgroups then wait on an unposted batch, see `stop` and exit.  Bounded wait.
   int persist_halt() {
     if (!prunning) return 0;
-    __atomic_store_n(&pctl->stop, 1ull, __ATOMIC_RELEASE);
-    const int64_t t0 = now_ns();
     hipError_t q;
-    while ((q = hipStreamQuery(pstream)) == hipErrorNotReady) {
-      if (now_ns() - t0 > 20ll * 1000000000ll) { set_error("persistent kernel did not stop"); return -6; }
-      std::this_thread::sleep_for(std::chrono::microseconds(20));
-    }
+    if (!persist_stop_wait(20ll * 1000000000ll, 20, &q)) { set_error("persistent kernel did not stop"); return -6; }
     prunning = false;
     if (q != hipSuccess) { set_error(std::string("persistent kernel: ") + hipGetErrorString(q)); return -4; }
     return 0;
   }
 
   void persist_free() {
-    if (!persistent) {                       // refused or failed part-way through persist_init
-      if (pstream) (void)hipStreamDestroy(pstream);
-      if (pdev) (void)hipFree(pdev);
-      if (pdesc) (void)hipHostFree(pdesc);
-      if (pctl) (void)hipHostFree(pctl);
-      pstream = nullptr; pdev = nullptr; pdesc = nullptr; pctl = nullptr;
-      if (persist_counted) g_persist_engines[cfg.device].fetch_sub(1);
-      persist_counted = false;
-      return;
-    }
-    // a completed batch the host never retired (scored-ring back-pressure, a held hand-off,
-    // an exception before the drain) stays busy: wait for it here and mark it retired -- its
-    // completion record lives in pctl, which is freed below (the slot loop in ~Engine must
-    // not read it afterwards)
-    for (auto& s : slots) {
-      if (s.busy) wait_done(s);
-      if (s.use_flag) { s.busy = false; s.use_flag = false; s.done_ptr = nullptr; }
-    }
-    persist_halt();
+    if (persistent) {
+      // a completed batch the host never retired (scored-ring back-pressure, a held hand-off,
+      // an exception before the drain) stays busy: wait for it here and mark it retired -- its
+      // completion record lives in pctl, which is freed below (the slot loop in ~Engine must
+      // not read it afterwards)
+      for (auto& s : slots) {
+        if (s.busy) wait_done(s);
+        if (s.use_flag) { s.busy = false; s.use_flag = false; s.done_ptr = nullptr; }
+      }
+      persist_halt();
 #ifdef CCFD_EXP_ITEM_TRACE
-    if (const char* out = std::getenv("CCFD_ITEM_TRACE_OUT")) {   // experiment build only
-      static int k = 0;
-      const std::string path = std::string(out) + "." + std::to_string(k++);
-      ccfd::item_trace_dump(path.c_str());
-    }
+      if (const char* out = std::getenv("CCFD_ITEM_TRACE_OUT")) {   // experiment build only
+        static int k = 0;
+        const std::string path = std::string(out) + "." + std::to_string(k++);
+        ccfd::item_trace_dump(path.c_str());
+      }
 #endif
-    // teardown: nothing useful can be done about a failed release, so results are dropped
-    (void)hipStreamDestroy(pstream);
-    (void)hipFree(pdev);
-    (void)hipHostFree(pdesc);
-    (void)hipHostFree(pctl);
+    }
+    // teardown (also of a persist_init refused or failed part-way through): nothing useful can
+    // be done about a failed release, so results are dropped
+    if (pstream) (void)hipStreamDestroy(pstream);
+    if (pdev) (void)hipFree(pdev);
+    if (pdesc) (void)hipHostFree(pdesc);
+    if (pctl) (void)hipHostFree(pctl);
+    pstream = nullptr; pdev = nullptr; pdesc = nullptr; pctl = nullptr;
     if (persist_counted) g_persist_engines[cfg.device].fetch_sub(1);
     persist_counted = false;
     persistent = false;
@@ -595,13 +441,12 @@ class Engine {
   }
 
   ~Engine() {
-    stamper_stop.store(true);
-    if (stamper.joinable()) stamper.join();
+    stamper.stop();                  // before the completion records it watches are freed
     if (std::getenv("CCFD_STAMPER_DEBUG"))
       std::fprintf(stderr, "[engine] completion stamps used %llu missed %llu rejected %llu written %llu iters %llu\n",
-                   (unsigned long long)stamp_used, (unsigned long long)stamp_missed,
-                   (unsigned long long)stamp_rejected, (unsigned long long)stamps_written.load(),
-                   (unsigned long long)stamper_iters.load());
+                   (unsigned long long)stamper.used, (unsigned long long)stamper.missed,
+                   (unsigned long long)stamper.rejected, (unsigned long long)stamper.written.load(),
+                   (unsigned long long)stamper.iters.load());
     (void)hipSetDevice(cfg.device);
     persist_free();
     if (sync_stage) (void)hipHostFree(sync_stage);
@@ -621,16 +466,16 @@ class Engine {
     for (auto st : streams) if (st) (void)hipStreamDestroy(st);
   }
 
-  int set_log(int p, const float* feats, const uint64_t* ids, const uint32_t* cust, int64_t n, int64_t cursor) {
-    if (p < 0 || p > 4096) { set_error("bad partition index"); return -1; }
-    if (n < cfg.max_batch) { set_error("partition log shorter than one micro-batch"); return -1; }
-    if (reinterpret_cast<uintptr_t>(feats) & 15) { set_error("log must be 16-byte aligned"); return -1; }
+  // (re)point partition `p` at a replay log (ring = false) or an ingest ring of `n` rows
+  int register_partition(int p, bool ring, const float* feats, const uint64_t* ids, const uint32_t* cust,
+                         int64_t n, int64_t cursor) {
     { int rc = drain_all(); if (rc) return rc; }
     while ((int)parts.size() <= p) parts.emplace_back(new Partition());
     Partition& P = *parts[p];
-    P.ring = false;
-    P.feats = feats; P.ids = ids; P.cust = cust; P.n = n; P.cursor = cursor % n;
+    P.ring = ring;
+    P.feats = feats; P.ids = ids; P.cust = cust; P.n = n; P.cursor = cursor;
     P.amount = nullptr;
+    if (ring) P.rr.reset(n);
     P.feats_dev = feats;
     if (cfg.input_mode == 1) {
       void* d = nullptr;
@@ -640,33 +485,75 @@ class Engine {
     return 0;
   }
 
-  void push_flagged_idx(const Slot& s, uint64_t nf) {
+  int set_log(int p, const float* feats, const uint64_t* ids, const uint32_t* cust, int64_t n, int64_t cursor) {
+    if (p < 0 || p > 4096) { set_error("bad partition index"); return -1; }
+    if (n < cfg.max_batch) { set_error("partition log shorter than one micro-batch"); return -1; }
+    if (reinterpret_cast<uintptr_t>(feats) & 15) { set_error("log must be 16-byte aligned"); return -1; }
+    return register_partition(p, false, feats, ids, cust, n, cursor % n);
+  }
+
+  // Where the rows of one batch are, by value: a push loop makes one of these before it
+  // starts, so what it reads per record sits in registers (stores into a ring record may alias
+  // the engine's own fields, and would otherwise force rowf, amount_f and the pointers to be
+  // re-read for every record).  fill() writes the fields that ccfd_flagged, ccfd_scored and the
+  // last-request record share.
+  struct BatchRows {
+    const uint64_t* ids;
+    const uint32_t* cust;
+    const float* feats;
+    const float* amount;
+    const float* proba;
+    int64_t start, rowf;
+    int amount_f;
+    uint64_t tx_id(int i) const { return ids ? ids[start + i] : (uint64_t)(start + i); }
+    float amount_of(int i) const {
+      const int64_t row = start + i;
+      return amount_f >= 0 ? feats[row * rowf + amount_f] : (amount ? amount[row] : __builtin_nanf(""));
+    }
+    template <class R>
+    void fill(R& r, int i) const {
+      r.tx_id = tx_id(i);
+      r.customer = cust ? cust[start + i] : 0u;
+      r.proba = proba[i];
+      r.amount = amount_of(i);
+    }
+  };
+  BatchRows rows_of(const Slot& s) const {
     const Partition& P = *parts[s.part];
-    std::lock_guard<std::mutex> lk(ring_mu);
-    const uint64_t cap = ring.size();
-    for (uint64_t k = 0; k < nf; ++k) emit(P, s, (int)s.h_flag[k], cap);
+    return BatchRows{P.ids, P.cust, P.feats, P.amount, s.h_proba, s.start, rowf, amount_f};
+  }
+
+  // complete() reserved room for the whole batch before calling in; a full ring here is a bug
+  // (the writer counts the record as dropped)
+  static void emit(ccfd::RecordRing<ccfd_flagged>::Writer& w, const BatchRows& b, uint32_t part, int i) {
+    ccfd_flagged* f = w.next();
+    if (!f) return;
+    b.fill(*f, i);
+    f->partition = part;
+  }
+
+  void push_flagged_idx(const Slot& s, uint64_t nf) {
+    const BatchRows b = rows_of(s);
+    const unsigned int* idx = s.h_flag;
+    const uint32_t part = (uint32_t)s.part;
+    auto w = flagged.writer();
+    for (uint64_t k = 0; k < nf; ++k) emit(w, b, part, (int)idx[k]);
   }
 
   void push_flagged(const Slot& s) {
-    const Partition& P = *parts[s.part];
+    const BatchRows b = rows_of(s);
+    const uint32_t part = (uint32_t)s.part;
     const uint8_t* r = s.h_route;
     const int n = s.rows;
-    std::lock_guard<std::mutex> lk(ring_mu);
-    const uint64_t cap = ring.size();
+    auto w = flagged.writer();
     int i = 0;
     for (; i + 8 <= n; i += 8) {
-      uint64_t w;
-      std::memcpy(&w, r + i, 8);
-      if (w == 0) continue;
-      for (int k = 0; k < 8; ++k) if (r[i + k]) emit(P, s, i + k, cap);
+      uint64_t v;
+      std::memcpy(&v, r + i, 8);
+      if (v == 0) continue;
+      for (int k = 0; k < 8; ++k) if (r[i + k]) emit(w, b, part, i + k);
     }
-    for (; i < n; ++i) if (r[i]) emit(P, s, i, cap);
-  }
-
-  // free records in the flagged ring (drainers only ever grow it)
-  uint64_t flag_room() {
-    std::lock_guard<std::mutex> lk(ring_mu);
-    return ring.size() - (ring_tail - ring_head);
+    for (; i < n; ++i) if (r[i]) emit(w, b, part, i);
   }
 
   // fraud-routed rows of a finished batch: the kernel-published count, or the route bytes
@@ -680,55 +567,23 @@ class Engine {
   // complete() found the batch's flagged records do not fit: nothing was retired
   static constexpr int kFlagFull = CCFD_ENGINE_FLAG_FULL;
 
-  inline void emit(const Partition& P, const Slot& s, int i, uint64_t cap) {
-    // complete() reserved room for the whole batch before calling in; reaching this is a bug
-    if (ring_tail - ring_head >= cap) { ++dropped; return; }
-    const int64_t row = s.start + i;
-    ccfd_flagged& f = ring[ring_tail % cap];
-    f.tx_id = P.ids ? P.ids[row] : (uint64_t)row;
-    f.customer = P.cust ? P.cust[row] : 0u;
-    f.proba = s.h_proba[i];
-    f.amount = amount_f >= 0 ? P.feats[row * rowf + amount_f] : (P.amount ? P.amount[row] : __builtin_nanf(""));
-    f.partition = (uint32_t)s.part;
-    ++ring_tail;
-  }
-
-  uint64_t scored_room() {
-    std::lock_guard<std::mutex> lk(s_mu);
-    return sring.size() - (s_tail - s_head);
-  }
-
   // every row of the completed batch `s` -> the scored ring (route from the kernel's route
   // byte, proba_1 from its output slot; both written by the epilogue before the completion
   // record); rows that do not fit are counted, never overwrite unread records
   void push_scored(const Slot& s) {
-    const Partition& P = *parts[s.part];
-    std::lock_guard<std::mutex> lk(s_mu);
-    const uint64_t cap = sring.size();
+    const BatchRows b = rows_of(s);
+    const uint8_t* route = s.h_route;
+    auto w = scored.writer();
     const int n = s.rows;
-    const uint64_t room = cap - (s_tail - s_head);
-    const int take = (int)std::min<uint64_t>(room, (uint64_t)n);
-    s_dropped += (uint64_t)(n - take);
+    const int take = (int)std::min<uint64_t>(w.room(), (uint64_t)n);
+    w.drop((uint64_t)(n - take));
     for (int i = 0; i < take; ++i) {
-      const int64_t row = s.start + i;
-      ccfd_scored& r = sring[s_tail % cap];
-      r.tx_id = P.ids ? P.ids[row] : (uint64_t)row;
-      r.customer = P.cust ? P.cust[row] : 0u;
-      r.proba = s.h_proba[i];
-      r.amount = amount_f >= 0 ? P.feats[row * rowf + amount_f] : (P.amount ? P.amount[row] : __builtin_nanf(""));
+      ccfd_scored& r = *w.next();
+      b.fill(r, i);
       r.partition = (uint16_t)s.part;
-      r.route = s.h_route[i] ? 1 : 0;
+      r.route = route[i] ? 1 : 0;
       r.pad = 0;
-      ++s_tail;
     }
-  }
-
-  int64_t drain_scored(ccfd_scored* out, int64_t max) {
-    std::lock_guard<std::mutex> lk(s_mu);
-    const uint64_t cap = sring.size();
-    int64_t k = 0;
-    while (s_head < s_tail && k < max) out[k++] = sring[s_head++ % cap];
-    return k;
   }
 
   bool is_done(const Slot& s) {
@@ -781,45 +636,20 @@ class Engine {
     const int64_t tw = now_ns();
     { int rc = wait_done(s); if (rc) return rc; }
     const int64_t t = now_ns();
-    t_wait_ns += t - tw;
+    lat.host_wait_ns += t - tw;
     const uint64_t nf_need = nflag_of(s);
-    if (nf_need && flag_room() < nf_need) { ++flag_full_events; return kFlagFull; }
+    if (nf_need && flagged.room() < nf_need) { ++flag_full_events; return kFlagFull; }
     const int64_t t0 = s.t_arrival ? s.t_arrival : s.t_submit;   // ring: end-to-end from commit
     const int64_t t_landed = landed_ns(s, t);                   // results in host memory
-    const double us = (t_landed - t0) * 1e-3;
-
-    ++lat_n;
-    lat_sum_us += us;
-    lat_max_us = std::max(lat_max_us, us);
-    {
-      const double fb = us / kFineUs;
-      if (fb < kFineBuckets) ++lat_fine[(size_t)fb]; else ++lat_over;
-    }
-    const double ns = (double)std::max<int64_t>(1, t_landed - t0);
-    {
-      const int b = std::min(255, (int)std::floor(4.0 * std::log2(ns)));
-      lat_hist[b]++;
-      lat_hist_rows[b] += (uint64_t)s.rows;
-    }
-    if (s.t_origin > 0 && t_landed > s.t_origin) {        // producer send -> results in host memory
-      const int b = std::min(255, (int)std::floor(4.0 * std::log2((double)(t_landed - s.t_origin))));
-      ++origin_batches;
-      origin_hist[b]++;
-      origin_hist_rows[b] += (uint64_t)s.rows;
-    }
+    // end to end, and producer send -> results in host memory where the send time is known
+    lat.record(t_landed - t0, s.t_origin > 0 ? t_landed - s.t_origin : 0, (uint64_t)s.rows);
     const uint64_t nf = nf_need;
     if (s.use_flag) {
       if (nf) push_flagged_idx(s, nf);
       {                                                // K7: device-clock execution window
         const uint64_t t0d = s.done_ptr[2], t1d = s.done_ptr[3];
-        if (t1d > t0d && wall_ns_per_tick > 0) {
-          const double dns = (double)(t1d - t0d) * wall_ns_per_tick;
-          dev_exec_ns += (uint64_t)dns;
-          ++dev_batches;
-          const int b = std::min(255, (int)std::floor(4.0 * std::log2(std::max(1.0, dns))));
-          dev_hist[b]++;
-          dev_hist_rows[b] += (uint64_t)s.rows;
-        }
+        if (t1d > t0d && wall_ns_per_tick > 0)
+          lat.record_device((double)(t1d - t0d) * wall_ns_per_tick, (uint64_t)s.rows);
       }
     } else if (nf) {
       push_flagged(s);
@@ -829,24 +659,24 @@ class Engine {
     if (trace_on.load(std::memory_order_relaxed)) record_trace(s, t_landed, nf);
     Partition& P = *parts[s.part];
     if (s.rows > 0 && P.feats) {                     // "last request" record (still unreleased)
-      const int64_t row = s.start + s.rows - 1;
-      std::memcpy(last_row, P.feats + row * rowf, (size_t)rowf * sizeof(float));
-      last_tx_id = P.ids ? P.ids[row] : (uint64_t)row;
-      last_proba = s.h_proba[s.rows - 1];
-      last_amount = amount_f >= 0 ? P.feats[row * rowf + amount_f] : (P.amount ? P.amount[row] : __builtin_nanf(""));
+      const BatchRows b = rows_of(s);
+      std::memcpy(last_row, P.feats + (s.start + s.rows - 1) * rowf, (size_t)rowf * sizeof(float));
+      last_tx_id = b.tx_id(s.rows - 1);
+      last_proba = b.proba[s.rows - 1];
+      last_amount = b.amount_of(s.rows - 1);
       last_partition = s.part;
       ++last_seq;
     }
     if (P.ring) {
       // batches of one partition complete in submission order: release in order
       P.rr.release_rows(s.rows);
-      P.forget_before(P.rr.released_count());
+      P.arrivals.forget_before(P.rr.released_count());
     }
     s.busy = false;
     s.t_arrival = 0;
     s.t_origin = 0;
     completed_upto = std::max<int64_t>(completed_upto, s.seq_no + 1);
-    t_complete_ns += now_ns() - t;
+    lat.host_complete_ns += now_ns() - t;
     return 0;
   }
 
@@ -869,7 +699,7 @@ class Engine {
              bool force_dma = false, bool force_zc = false) {
     s.t_submit = now_ns();
     s.seq_no = (int64_t)seq;
-    struct Acc { uint64_t& a; int64_t t0; ~Acc() { a += now_ns() - t0; } } acc{t_submit_ns, s.t_submit};
+    SubmitTimer acc{lat.host_submit_ns, s.t_submit};
     const float* xk = x_dev_or_host;
     if (persistent) {
       if ((cfg.input_mode == 0 || force_dma) && !force_zc) {
@@ -940,7 +770,7 @@ class Engine {
     Partition& P = *parts[p];
     const int D = (int)slots.size();
     const int64_t t = now_ns();
-    struct Acc { uint64_t& a; int64_t t0; ~Acc() { a += now_ns() - t0; } } acc{t_submit_ns, t};
+    SubmitTimer acc{lat.host_submit_ns, t};
     ccfd_multi_args m{};
     ccfd_score_args& a = m.base;
     a.x = P.feats_dev + (size_t)start * rowf;
@@ -983,9 +813,7 @@ class Engine {
       if (st) {
         st->submitted += (uint64_t)b;
         st->wall_s += (now_ns() - t0) * 1e-9;
-        st->flagged_dropped = dropped;
-        st->flag_full_events = flag_full_events;
-        fill_latency(st);
+        report(st);
       }
       return rc;
     };
@@ -1024,39 +852,11 @@ class Engine {
     return finish(drain ? drain_all(st) : 0);
   }
 
-  // nearest-rank quantile from the fine histogram (bucket midpoint); samples beyond its
-  // range report the max
-  double fine_quantile(double q) const {
-    const uint64_t k = (uint64_t)std::floor(q * (double)(lat_n - 1) + 0.5);
-    uint64_t c = 0;
-    for (int i = 0; i < kFineBuckets; ++i) {
-      c += lat_fine[i];
-      if (c > k) return (i + 0.5) * kFineUs;
-    }
-    return lat_max_us;
-  }
-
-  void reset_latency() {
-    lat_n = lat_over = 0;
-    lat_sum_us = lat_max_us = 0.0;
-    std::fill(lat_fine.begin(), lat_fine.end(), 0ull);
-    std::memset(lat_hist, 0, sizeof(lat_hist));
-    std::memset(lat_hist_rows, 0, sizeof(lat_hist_rows));
-    origin_batches = 0;
-    std::memset(origin_hist, 0, sizeof(origin_hist));
-    std::memset(origin_hist_rows, 0, sizeof(origin_hist_rows));
-  }
-
-  void fill_latency(ccfd_engine_stats* st) {
-    std::memcpy(st->lat_hist, lat_hist, sizeof(lat_hist));
-    st->host_submit_ns = t_submit_ns;
-    st->host_wait_ns = t_wait_ns;
-    st->host_complete_ns = t_complete_ns;
-    st->dev_batches = dev_batches;
-    st->dev_exec_ns = dev_exec_ns;
-    std::memcpy(st->dev_hist, dev_hist, sizeof(dev_hist));
-    std::memcpy(st->lat_hist_rows, lat_hist_rows, sizeof(lat_hist_rows));
-    std::memcpy(st->dev_hist_rows, dev_hist_rows, sizeof(dev_hist_rows));
+  // everything in `st` that is engine state rather than this call's counts
+  void report(ccfd_engine_stats* st) {
+    st->flagged_dropped = flagged.dropped();
+    st->flag_full_events = flag_full_events;
+    lat.fill(st);
     st->last_seq = last_seq;
     st->last_tx_id = last_tx_id;
     st->last_proba = last_proba;
@@ -1064,14 +864,6 @@ class Engine {
     st->last_partition = last_partition;
     st->last_row_bytes = rowf * (int32_t)sizeof(float);
     std::memcpy(st->last_row, last_row, sizeof(last_row));
-    st->origin_batches = origin_batches;
-    std::memcpy(st->origin_hist, origin_hist, sizeof(origin_hist));
-    std::memcpy(st->origin_hist_rows, origin_hist_rows, sizeof(origin_hist_rows));
-    if (lat_n == 0) return;
-    st->lat_p50_us = fine_quantile(0.50);
-    st->lat_p99_us = fine_quantile(0.99);
-    st->lat_max_us = lat_max_us;
-    st->lat_mean_us = lat_sum_us / (double)lat_n;
   }
 
   int score_sync(const float* x, int32_t n, float* proba_out, uint8_t* route_out) {
@@ -1085,15 +877,9 @@ class Engine {
       hipStream_t stream = streams[seq % streams.size()];
       const float* xh = x + (size_t)off * rowf;
       if (rows <= sync_zc_rows) {
-        if (!sync_stage) {
-          void* p = nullptr;
-          HIPCHK(hipHostMalloc(&p, (size_t)sync_zc_rows * rowf * sizeof(float),
-                               hipHostMallocMapped | hipHostMallocPortable | hipHostMallocCoherent));
-          sync_stage = static_cast<float*>(p);
-          void* d = nullptr;
-          HIPCHK(hipHostGetDevicePointer(&d, p, 0));
-          sync_stage_dev = static_cast<const float*>(d);
-        }
+        if (!sync_stage)
+          if (int arc = alloc_mapped(&sync_stage, &sync_stage_dev, (size_t)sync_zc_rows * rowf * sizeof(float), false))
+            return arc;
         // the previous batch has completed (wait_done below), so the stage is free
         std::memcpy(sync_stage, xh, (size_t)rows * rowf * sizeof(float));
         rc = submit(s, sync_stage_dev, sync_stage, rows, stream, /*force_dma=*/false, /*force_zc=*/true);
@@ -1113,15 +899,20 @@ class Engine {
     return persistent ? persist_halt() : 0;
   }
 
+  // every in-flight micro-batch completes and a resident persistent kernel halts
+  int quiesce() {
+    HIPCHK(hipSetDevice(cfg.device));
+    int rc = drain_all();
+    if (rc) return rc;
+    return persistent && prunning ? persist_halt() : 0;
+  }
+
   // Model hot swap (X1 at runtime): every in-flight micro-batch completes with the old
   // weights (and a resident persistent kernel halts), then later submissions read `blob`.
   // The caller keeps the old blob alive until this returns.
   int set_blob(const void* blob) {
     if (blob == nullptr) { set_error("null model blob"); return -1; }
-    HIPCHK(hipSetDevice(cfg.device));
-    int rc = drain_all();
-    if (rc) return rc;
-    if (persistent && prunning) { rc = persist_halt(); if (rc) return rc; }
+    if (int rc = quiesce()) return rc;
     cfg.blob = blob;
     return 0;
   }
@@ -1150,22 +941,19 @@ class Engine {
         set_error("shadow model refused: the engine routes by a rule program; shadow scoring routes by threshold only");
         return -1;
       }
-      if (persistent && persist_pipe) {
+      if (persistent && plan.pipe) {
         set_error("shadow model refused: pipelined persistent items (persist_items = 2 / CCFD_PERSIST_PIPE) "
                   "have no shadow kernel; use claimed items");
         return -1;
       }
       // a GBDT champion's items (256 / 512 / 1024 rows) all have a shadow kernel
-      if (!gbdt && persistent && persist_tpw != 2 && persist_tpw != 4 && persist_tpw != 8) {
-        set_error("shadow model refused: persistent items of " + std::to_string(64 * persist_tpw) +
+      if (!gbdt && persistent && plan.tiles_per_wave != 2 && plan.tiles_per_wave != 4 && plan.tiles_per_wave != 8) {
+        set_error("shadow model refused: persistent items of " + std::to_string(64 * plan.tiles_per_wave) +
                   " rows; the shadow kernel takes items of 128, 256 or 512 rows");
         return -1;
       }
     }
-    HIPCHK(hipSetDevice(cfg.device));
-    int rc = drain_all();
-    if (rc) return rc;
-    if (persistent && prunning) { rc = persist_halt(); if (rc) return rc; }
+    if (int rc = quiesce()) return rc;
     shadow_blob = blob;
     return 0;
   }
@@ -1193,21 +981,7 @@ class Engine {
   int set_ring(int p, float* feats, uint64_t* ids, uint32_t* cust, int64_t cap) {
     if (p < 0 || p > 4096 || cap < cfg.max_batch) { set_error("bad ring partition/capacity"); return -1; }
     if (reinterpret_cast<uintptr_t>(feats) & 15) { set_error("ring must be 16-byte aligned"); return -1; }
-    int rc = drain_all();
-    if (rc) return rc;
-    while ((int)parts.size() <= p) parts.emplace_back(new Partition());
-    Partition& P = *parts[p];
-    P.ring = true;
-    P.feats = feats; P.ids = ids; P.cust = cust; P.n = cap; P.cursor = 0;
-    P.amount = nullptr;
-    P.rr.reset(cap);
-    P.feats_dev = feats;
-    if (cfg.input_mode == 1) {
-      void* d = nullptr;
-      HIPCHK(hipHostGetDevicePointer(&d, feats, 0));
-      P.feats_dev = static_cast<const float*>(d);
-    }
-    return 0;
+    return register_partition(p, true, feats, ids, cust, cap, 0);
   }
 
   // Producer side: contiguous free rows starting at physical *row (0 if the ring is full).
@@ -1219,11 +993,8 @@ class Engine {
   int ring_commit(int p, int64_t n, int64_t origin_ns = 0) {
     if (p < 0 || p >= (int)parts.size() || !parts[p]->ring) return -1;
     Partition& P = *parts[p];
-    {
-      std::lock_guard<std::mutex> lk(P.arr_mu);
-      const int64_t t = now_ns();
-      P.arrivals.push_back(Partition::Arrival{P.rr.head_count() + n, t, origin_ns > 0 && origin_ns <= t ? origin_ns : 0});
-    }
+    const int64_t t = now_ns();
+    P.arrivals.push(P.rr.head_count() + n, t, origin_ns > 0 && origin_ns <= t ? origin_ns : 0);
     P.rr.commit(n);                    // publish after the arrival stamp exists
     return 0;
   }
@@ -1257,7 +1028,7 @@ class Engine {
         if (!is_done(s)) break;
         // scored ring full: leave the batch (and its ring rows) in place until the consumer
         // drains -- back-pressure reaches ingest instead of losing standard-route records
-        if (scored_on.load(std::memory_order_relaxed) && scored_room() < (uint64_t)s.rows) break;
+        if (scored_on.load(std::memory_order_relaxed) && scored.room() < (uint64_t)s.rows) break;
         // flagged ring full: the same -- the batch waits for the hand-off consumer (never dropped)
         int rc = complete(s, st);
         if (rc == kFlagFull) break;
@@ -1283,7 +1054,7 @@ class Engine {
             int rc = submit_multi((int)q, phys, cfg.max_batch, K);
             if (rc) return rc;
             for (int k = 0; k < K; ++k) {
-              const Partition::Arrival a = P.arrival_of(P.rr.taken() + (int64_t)k * cfg.max_batch);
+              const ccfd::ArrivalLog::Arrival a = P.arrivals.arrival_of(P.rr.taken() + (int64_t)k * cfg.max_batch);
               slots[(seq + k) % D].t_arrival = a.t;
               slots[(seq + k) % D].t_origin = a.origin;
             }
@@ -1296,7 +1067,7 @@ class Engine {
           }
           int64_t rows = std::min<int64_t>({avail, (int64_t)cfg.max_batch, P.n - phys});
           const bool full = rows == cfg.max_batch || rows == P.n - phys;
-          const Partition::Arrival arr_rec = P.arrival_of(P.rr.taken());
+          const ccfd::ArrivalLog::Arrival arr_rec = P.arrivals.arrival_of(P.rr.taken());
           const int64_t arr = arr_rec.t;
           // a partial batch waits for more rows until its deadline -- unless the GPU has
           // nothing in flight (work-conserving: at low / moderate arrival rates a row is
@@ -1330,10 +1101,8 @@ class Engine {
     }
     if (st) {
       st->wall_s += (now_ns() - t0) * 1e-9;
-      st->flagged_dropped = dropped;
-      st->flag_full_events = flag_full_events;
       st->submitted += (uint64_t)submitted;
-      fill_latency(st);
+      report(st);
     }
     return submitted;
   }
@@ -1391,14 +1160,6 @@ class Engine {
     if (serve_th.joinable()) serve_th.join();
     serving.store(false);
     return serve_rc.load();
-  }
-
-  int64_t drain_flagged(ccfd_flagged* out, int64_t max) {
-    std::lock_guard<std::mutex> lk(ring_mu);
-    const uint64_t cap = ring.size();
-    int64_t k = 0;
-    while (ring_head < ring_tail && k < max) out[k++] = ring[ring_head++ % cap];
-    return k;
   }
 };
 
@@ -1459,11 +1220,9 @@ int ccfd_engine_serve_collect(void* eng, ccfd_engine_stats* out, ccfd_flagged* f
   if (!out || !n_flagged || (max_flagged > 0 && !flagged)) return -1;
   ApiLock lk(e);                       // no batch completes while the three are read
   *out = e->serve_st;
-  e->fill_latency(out);
-  out->flagged_dropped = e->dropped;
-  out->flag_full_events = e->flag_full_events;
-  *n_flagged = e->drain_flagged(flagged, max_flagged);
-  if (n_scored) *n_scored = (scored && max_scored > 0) ? e->drain_scored(scored, max_scored) : 0;
+  e->report(out);
+  *n_flagged = e->flagged.drain(flagged, max_flagged);
+  if (n_scored) *n_scored = (scored && max_scored > 0) ? e->scored.drain(scored, max_scored) : 0;
   return e->serve_rc.load();
 }
 
@@ -1472,9 +1231,7 @@ int ccfd_engine_serve_stats(void* eng, ccfd_engine_stats* out, int64_t* iters) {
   if (!out) return -1;
   ApiLock lk(e);
   *out = e->serve_st;
-  e->fill_latency(out);
-  out->flagged_dropped = e->dropped;
-  out->flag_full_events = e->flag_full_events;
+  e->report(out);
   if (iters) *iters = (int64_t)e->serve_iters;
   return e->serve_rc.load();
 }
@@ -1517,7 +1274,7 @@ int ccfd_engine_set_shadow(void* eng, const void* blob) {
 }
 
 int64_t ccfd_engine_drain_flagged(void* eng, ccfd_flagged* out, int64_t max) {
-  return static_cast<Engine*>(eng)->drain_flagged(out, max);
+  return static_cast<Engine*>(eng)->flagged.drain(out, max);
 }
 
 int ccfd_engine_scored_enable(void* eng, int64_t capacity) {
@@ -1526,22 +1283,18 @@ int ccfd_engine_scored_enable(void* eng, int64_t capacity) {
   ApiLock lk(e);
   int rc = e->drain_all();
   if (rc) return rc;
-  std::lock_guard<std::mutex> slk(e->s_mu);
-  e->sring.assign((size_t)capacity, ccfd_scored{});
-  e->s_head = e->s_tail = e->s_dropped = 0;
+  e->scored.reset((size_t)capacity);
   e->scored_on.store(capacity > 0, std::memory_order_relaxed);
   return 0;
 }
 
 int64_t ccfd_engine_drain_scored(void* eng, ccfd_scored* out, int64_t max) {
   if (!eng || (!out && max > 0) || max < 0) return -1;
-  return static_cast<Engine*>(eng)->drain_scored(out, max);
+  return static_cast<Engine*>(eng)->scored.drain(out, max);
 }
 
 int64_t ccfd_engine_scored_dropped(void* eng) {
-  auto* e = static_cast<Engine*>(eng);
-  std::lock_guard<std::mutex> lk(e->s_mu);
-  return (int64_t)e->s_dropped;
+  return (int64_t)static_cast<Engine*>(eng)->scored.dropped();
 }
 
 int64_t ccfd_engine_cursor(void* eng, int partition) {
@@ -1574,13 +1327,8 @@ int ccfd_engine_progress(void* eng, int64_t* out) {
 int ccfd_engine_emergency_stop(void* eng, int timeout_ms) {
   auto* e = static_cast<Engine*>(eng);
   if (!e->persistent || !e->pctl || !e->prunning) return 0;
-  __atomic_store_n(&e->pctl->stop, 1ull, __ATOMIC_RELEASE);
-  const int64_t t0 = now_ns();
-  while (hipStreamQuery(e->pstream) == hipErrorNotReady) {
-    if (now_ns() - t0 > (int64_t)timeout_ms * 1000000ll) return -6;
-    std::this_thread::sleep_for(std::chrono::microseconds(200));
-  }
-  return 0;
+  hipError_t q;
+  return e->persist_stop_wait((int64_t)timeout_ms * 1000000ll, 200, &q) ? 0 : -6;
 }
 
 int ccfd_engine_set_amount(void* eng, int partition, const float* amount) {
@@ -1644,11 +1392,7 @@ int ccfd_engine_trace_read(void* eng, ccfd_batch_trace* out, int32_t max) {
 void ccfd_engine_reset_stats(void* eng) {
   auto* e = static_cast<Engine*>(eng);
   ApiLock lk(e);
-  e->reset_latency();
-  e->t_submit_ns = e->t_wait_ns = e->t_complete_ns = 0;
-  e->dev_batches = e->dev_exec_ns = 0;
-  std::memset(e->dev_hist, 0, sizeof(e->dev_hist));
-  std::memset(e->dev_hist_rows, 0, sizeof(e->dev_hist_rows));
+  e->lat.reset_all();
 }
 
 }  // extern "C"

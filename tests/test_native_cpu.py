@@ -74,6 +74,59 @@ def test_spsc_ring_stress_under_sanitizers(tmp_path, sanitizer):
     assert "ring stress ok" in out.stdout
 
 
+def _run_native_check(tmp_path, name, sanitizer, ok_line, args=()):
+    """Compile csrc/tests/<name>.cpp stand-alone (one main, only HIP-free engine headers), with
+    the sanitizer if one is given, and run the program directly."""
+    from ccfd_demo_summit_amd.ops.build import CSRC
+    exe = tmp_path / name
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-pthread", "-I", str(CSRC / "include"),
+           str(CSRC / "tests" / f"{name}.cpp"), "-o", str(exe)]
+    # plain first: broken code fails the test, only a missing sanitizer runtime may skip it
+    r = subprocess.run(cmd, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-3000:]
+    if sanitizer:
+        r = subprocess.run(cmd + [f"-fsanitize={sanitizer}"], capture_output=True, text=True)
+        if r.returncode != 0:
+            pytest.skip(f"sanitizer build unavailable: {r.stderr[-300:]}")
+    out = subprocess.run([str(exe), *args], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    assert ok_line in out.stdout
+
+
+def test_latency_stats_under_asan(tmp_path):
+    """The engine's latency statistics (csrc/engine/lat_stats.h): log-histogram buckets and row
+    weighting, nearest-rank quantiles against the rule computed from a sorted copy, over-range
+    and single-sample sets, and the exact field lists of the two resets."""
+    _run_native_check(tmp_path, "lat_stats_check", "address,undefined", "lat stats check ok")
+
+
+@pytest.mark.parametrize("sanitizer", ["thread", "address,undefined"])
+def test_record_ring_stress_under_sanitizers(tmp_path, sanitizer):
+    """The flagged / scored record ring (csrc/engine/record_ring.h): one producer, two drainers;
+    lossless with room reserved first, and accepted + dropped = pushed with nothing unread
+    overwritten when the producer never waits."""
+    _run_native_check(tmp_path, "record_ring_stress", sanitizer, "record ring stress ok")
+
+
+def test_completion_stamper_stress_under_tsan(tmp_path):
+    """The completion stamper thread (csrc/engine/completion_stamper.h): accepted stamps lie
+    between submit and fallback and belong to the awaited sequence, a stale word of the same
+    tag is rejected, every armed landed_ns() call is counted once, destruction with armed slots."""
+    _run_native_check(tmp_path, "stamper_stress", "thread", "stamper stress ok")
+
+
+def test_arrival_log_stress_under_tsan(tmp_path):
+    """The per-partition arrival log (csrc/engine/arrival_log.h): a committer and a reader that
+    looks rows up and forgets behind itself; every answer is the smallest recorded head > row."""
+    _run_native_check(tmp_path, "arrival_log_stress", "thread", "arrival log stress ok")
+
+
+def test_persist_plan_table(tmp_path):
+    """The persistent kernels' item / grid rules (csrc/engine/persist_plan.h) against a table of
+    expected plans written out as literals, each also with persist_grid overriding the grid."""
+    _run_native_check(tmp_path, "persist_plan_check", "", "persist plan check ok")
+
+
 def test_dedupe_index_stress_under_asan(tmp_path):
     """The KIE tier's windowed dedupe index (csrc/engine/dedupe.cpp) against a reference model
     under ASan/UBSan: repeats within and across batches, keys re-admitted after leaving the
