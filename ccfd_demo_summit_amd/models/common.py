@@ -88,6 +88,17 @@ class Normalizer:
                    bool(int(np.asarray(st["norm.log_amount"]).reshape(-1)[0])))
 
 
+def baseline_row(X: np.ndarray, how: str = "median") -> np.ndarray:
+    """float32 [30]: the per-feature median or mean of the rows ``X`` (the MLP / LR explain baseline)."""
+    X = np.asarray(X, np.float32)
+    if X.ndim != 2 or X.shape[1] != N_FEATURES or X.shape[0] < 1:
+        raise ValueError("baseline rows must be float32 [n >= 1, 30]")
+    if how not in ("median", "mean"):
+        raise ValueError(f"how must be 'median' or 'mean', not {how!r}")
+    b = np.median(X.astype(np.float64), axis=0) if how == "median" else X.astype(np.float64).mean(0)
+    return b.astype(np.float32)
+
+
 def header(magic: bytes, flags: int, *vals) -> bytes:
     """64-byte blob header: magic[4], flags u32, then up to 14 float32/int32 words."""
     assert len(magic) == 4

@@ -5,13 +5,13 @@
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Optional
 
 import numpy as np
 
 from ..contracts.transaction import N_FEATURES
-from .common import KPAD, Normalizer, header, sigmoid
+from .common import KPAD, Normalizer, baseline_row, header, sigmoid
 
 BLOB_BYTES = 64 + 3 * KPAD * 4
 
@@ -22,6 +22,7 @@ class LogisticModel:
     b: float
     norm: Normalizer
     kind: str = "lr"
+    baseline: Optional[np.ndarray] = None   # float32 [30]: the row the closed-form Shapley values start from
 
     @classmethod
     def random_init(cls, seed: int = 0, norm: Optional[Normalizer] = None) -> "LogisticModel":
@@ -44,6 +45,11 @@ class LogisticModel:
     def calibrate_bias(self, X: np.ndarray, target_rate: float, threshold: float = 0.5) -> None:
         z = self.logits(X)
         self.b += float(np.log(threshold / (1 - threshold)) - np.quantile(z, 1.0 - target_rate))
+
+    def fit_baseline(self, X: np.ndarray, how: str = "median") -> "LogisticModel":
+        """A copy whose ``baseline`` is the per-feature median (or mean) of ``X``: the background
+        row of ``models.explain_mlp.shapley_lr``."""
+        return replace(self, baseline=baseline_row(X, how))
 
     def pack(self, wire: bool = False) -> bytes:
         """``wire=True``: weights in W64 row order with the WHOLE normaliser folded in
@@ -70,9 +76,12 @@ class LogisticModel:
     def state_dict(self) -> dict:
         st = {"lr.w": self.w, "lr.b": np.array([self.b], np.float32)}
         st.update(self.norm.state())
+        if self.baseline is not None:
+            st["lr.baseline"] = np.asarray(self.baseline, np.float32)
         return st
 
     @classmethod
     def from_state_dict(cls, st: dict) -> "LogisticModel":
         return cls(np.asarray(st["lr.w"], np.float32), float(np.asarray(st["lr.b"]).reshape(-1)[0]),
-                   Normalizer.from_state(st))
+                   Normalizer.from_state(st),
+                   baseline=np.asarray(st["lr.baseline"], np.float32) if "lr.baseline" in st else None)

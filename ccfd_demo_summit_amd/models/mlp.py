@@ -39,13 +39,14 @@ Blob layout (bytes, all 16-B aligned), ``BLOB_BYTES`` = 25920:
 """
 from __future__ import annotations
 
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Optional
 
 import numpy as np
 
 from ..contracts.transaction import AMOUNT_COL, N_FEATURES, TIME_COL, WIRE_PERM, decode_wire, encode_wire
-from .common import (FLAG_WIRE, HEADER_BYTES, KPAD, Normalizer, bf16_bits, bf16_round, header, sigmoid)
+from .common import (FLAG_WIRE, HEADER_BYTES, KPAD, Normalizer, baseline_row, bf16_bits, bf16_round, header,
+                     sigmoid)
 
 H1, H2 = 128, 64
 OFF_NORM = HEADER_BYTES
@@ -78,6 +79,7 @@ class MLPModel:
     b3: float
     norm: Normalizer
     kind: str = "mlp"
+    baseline: Optional[np.ndarray] = None   # float32 [30]: the row sampled Shapley values start from
 
     @property
     def n_params(self) -> int:
@@ -122,6 +124,11 @@ class MLPModel:
         zt = np.log(threshold / (1.0 - threshold))
         q = np.quantile(z, 1.0 - target_rate)
         self.b3 += float(zt - q)
+
+    def fit_baseline(self, X: np.ndarray, how: str = "median") -> "MLPModel":
+        """A copy whose ``baseline`` is the per-feature median (or mean) of ``X``: the background
+        row of the sampled Shapley attributions (models/explain_mlp.py)."""
+        return replace(self, baseline=baseline_row(X, how))
 
     # ---------------------------------------------------------------- packing
     def _wire_w1(self):
@@ -213,6 +220,8 @@ class MLPModel:
         st = {"mlp.W1": self.W1, "mlp.b1": self.b1, "mlp.W2": self.W2, "mlp.b2": self.b2,
               "mlp.w3": self.w3, "mlp.b3": np.array([self.b3], np.float32)}
         st.update(self.norm.state())
+        if self.baseline is not None:
+            st["mlp.baseline"] = np.asarray(self.baseline, np.float32)
         return st
 
     @classmethod
@@ -220,7 +229,8 @@ class MLPModel:
         return cls(np.asarray(st["mlp.W1"], np.float32), np.asarray(st["mlp.b1"], np.float32),
                    np.asarray(st["mlp.W2"], np.float32), np.asarray(st["mlp.b2"], np.float32),
                    np.asarray(st["mlp.w3"], np.float32), float(np.asarray(st["mlp.b3"]).reshape(-1)[0]),
-                   Normalizer.from_state(st))
+                   Normalizer.from_state(st),
+                   baseline=np.asarray(st["mlp.baseline"], np.float32) if "mlp.baseline" in st else None)
 
 
 def emulate_packed_kernel(blob: bytes, X: np.ndarray) -> np.ndarray:

@@ -86,6 +86,15 @@ class ForestExplainArgs(C.Structure):    # ccfd_forest_explain_args
                 ("paths", C.c_int32), ("width", C.c_int32), ("slices", C.c_int32), ("rec_words", C.c_int32)]
 
 
+MLX_MAX_PERMS = 256                     # ccfd_abi.h CCFD_MLX_MAX_PERMS
+
+
+class MlpExplainArgs(C.Structure):       # ccfd_mlp_explain_args
+    _fields_ = [("rows", C.c_void_p), ("blob", C.c_void_p), ("table", C.c_void_p), ("phi", C.c_void_p),
+                ("z_out", C.c_void_p), ("n", C.c_int64), ("table_bytes", C.c_int64), ("blob_bytes", C.c_int64),
+                ("perms", C.c_int32), ("max_workgroups", C.c_int32), ("table_head", C.c_uint32 * 2)]
+
+
 DRIFT_COLS, DRIFT_CELLS = 31, 256       # ccfd_abi.h CCFD_DRIFT_*
 
 
@@ -175,6 +184,8 @@ def lib() -> C.CDLL:
         L.ccfd_forest_explain_launch.restype = C.c_int
         L.ccfd_forest_explain_workspace_bytes.argtypes = [C.c_int64, C.c_int32]
         L.ccfd_forest_explain_workspace_bytes.restype = C.c_int64
+        L.ccfd_mlp_explain_launch.argtypes = [C.POINTER(MlpExplainArgs), C.c_void_p]
+        L.ccfd_mlp_explain_launch.restype = C.c_int
         L.ccfd_drift_hist_launch.argtypes = [C.POINTER(DriftHistArgs), C.c_void_p]
         L.ccfd_drift_hist_launch.restype = C.c_int
         L.ccfd_forest_blob_changed.argtypes = [C.c_void_p]

@@ -15,7 +15,7 @@ import torch
 
 from ._lib import (ARG_WIRE_G20, ARG_WIRE_G32, ARG_WIRE_W64, BIN_FORMATS, DRIFT_CELLS, DRIFT_COLS, GBDT_MAX_SPLITS,
                    MODEL_IDS, N_COUNTER_SLOTS, DriftHistArgs, ForestExplainArgs, GbdtExplainArgs, GbdtHistArgs,
-                   GbdtUpdateArgs, ScoreArgs, ShadowArgs, check, lib)
+                   GbdtUpdateArgs, MlpExplainArgs, ScoreArgs, ShadowArgs, check, lib)
 
 N_FEATURES = 30
 ROW_BYTES = {"f32": 4 * N_FEATURES, "w64": 64, "g32": 32, "g20": 20}
@@ -400,6 +400,81 @@ def explain_forest(ex: DeviceExplainer, rows: torch.Tensor, out: Optional[torch.
     a.n, a.blob_bytes = n, ex.blob.numel()
     a.paths, a.width, a.slices, a.rec_words = ex.paths, ex.width, ex.slices, ex.rec_words
     check(lib().ccfd_forest_explain_launch(C.byref(a), C.c_void_p(s.cuda_stream)), "ccfd_forest_explain_launch")
+    return out
+
+
+class DeviceMlpExplainer:
+    """The W64 wire blob of an MLP with a baseline (``MLPModel.fit_baseline``) and the 'MLX1'
+    table of ``perms`` sampled permutations (``models.explain_mlp.MlpExplainTable``) resident in
+    HBM, for ``explain_mlp``.  ``base_value`` is the baseline's wire logit;
+    ``base_value + phi.sum(1)`` is the row's logit for every ``perms``."""
+
+    kind = "mlp"
+
+    def __init__(self, model, perms: int = 64, seed: int = 0, device: torch.device | str | int = "cuda"):
+        if getattr(model, "kind", None) != "mlp":
+            raise ValueError(f"no sampled-Shapley kernel for model kind {getattr(model, 'kind', None)!r} (MLP only; "
+                             "LR has the closed form models.explain_mlp.shapley_lr)")
+        from ..models.explain_mlp import MlpExplainTable, mlp_base_value
+        packed = MlpExplainTable.pack(model, perms, seed)          # refuses a model without baseline
+        self.perms, self.seed = int(perms), int(seed)
+        self.base_value = mlp_base_value(model)
+        self.table_head = tuple(int(v) for v in np.frombuffer(packed, np.uint32, 2, 0))
+        self.table = torch.from_numpy(np.frombuffer(packed, np.uint8).copy()).to(device)
+        self.blob = torch.from_numpy(np.frombuffer(model.pack(wire=True), np.uint8).copy()).to(self.table.device)
+        self.device = self.table.device
+
+    def explain(self, X: np.ndarray) -> Tuple[np.ndarray, float]:
+        """float32 [n,30] host rows -> (phi float32 [n,30] numpy, base_value)."""
+        from ..contracts.transaction import encode_wire
+        X = np.ascontiguousarray(X, np.float32)
+        if X.ndim != 2 or X.shape[1] != N_FEATURES:
+            raise ValueError("X must be float32 [n, 30]")
+        rows = torch.from_numpy(encode_wire(X)).to(self.device)
+        return explain_mlp(self, rows).cpu().numpy(), self.base_value
+
+
+MLP_EXPLAIN_WORKGROUPS = 2048       # default upper bound on explain_mlp's grid (4 rows a workgroup at a time)
+
+
+def explain_mlp(ex: DeviceMlpExplainer, rows: torch.Tensor, out: Optional[torch.Tensor] = None,
+                z_out: Optional[torch.Tensor] = None, stream: Optional[torch.cuda.Stream] = None,
+                max_workgroups: int = MLP_EXPLAIN_WORKGROUPS) -> torch.Tensor:
+    """Sampled Shapley values (logit space) of W64 ``rows`` ([n,64] u8, CUDA) under ``ex``'s MLP,
+    baseline and permutations (csrc/kernels/explain_mlp.hip; definition in docs/EXPLAIN.md):
+    returns ``phi`` float32 ``[n, 30]`` in canonical feature order (``out=`` reuses such a tensor).
+    ``z_out``: a float32 ``[n, perms, 32]`` tensor that receives every coalition row's logit.
+    A position whose bits equal the baseline's gets exactly 0.  The sum over permutations has a
+    fixed order: two runs, any ``max_workgroups`` (the upper bound on the grid) and any batch
+    around a row give that row identical bits."""
+    if not isinstance(ex, DeviceMlpExplainer):
+        raise ValueError("explain_mlp needs a DeviceMlpExplainer (tree models: DeviceExplainer and explain_gbdt / "
+                         "explain_forest)")
+    rb = ROW_BYTES["w64"]
+    if not rows.is_cuda or rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != rb or \
+            not rows.is_contiguous():
+        raise ValueError(f"rows must be contiguous CUDA W64 rows ([n,{rb}] u8)")
+    if rows.device != ex.device:
+        raise ValueError("rows must be on the explainer's device")
+    n = rows.shape[0]
+    shape = (n, N_FEATURES)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=rows.device)
+    elif not out.is_cuda or out.device != rows.device or out.dtype != torch.float32 or tuple(out.shape) != shape or \
+            not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous CUDA float32 tensor of shape {list(shape)} on the rows' device")
+    zshape = (n, ex.perms, 32)
+    if z_out is not None and (not z_out.is_cuda or z_out.device != rows.device or z_out.dtype != torch.float32 or
+                              tuple(z_out.shape) != zshape or not z_out.is_contiguous()):
+        raise ValueError(f"z_out must be a contiguous CUDA float32 tensor of shape {list(zshape)} on the rows' device")
+    a = MlpExplainArgs()
+    a.rows, a.blob, a.table, a.phi = rows.data_ptr(), ex.blob.data_ptr(), ex.table.data_ptr(), out.data_ptr()
+    a.z_out = z_out.data_ptr() if z_out is not None else None
+    a.n, a.table_bytes, a.blob_bytes = n, ex.table.numel(), ex.blob.numel()
+    a.perms, a.max_workgroups = ex.perms, int(max_workgroups)
+    a.table_head[0], a.table_head[1] = ex.table_head
+    s = stream if stream is not None else torch.cuda.current_stream(rows.device)
+    check(lib().ccfd_mlp_explain_launch(C.byref(a), C.c_void_p(s.cuda_stream)), "ccfd_mlp_explain_launch")
     return out
 
 

@@ -5,9 +5,9 @@
                     (pageable host input is staged by DMA; results come back pinned).
 
 Both return ``(proba_1 float32[n], route uint8[n])`` with route = proba >= threshold.
-``explain(X)`` (an oblivious GBDT or a general tree ensemble, with cover; anything else raises
-``ValueError``) returns ``(phi float32/64 [n,30], base_value)``, the exact Shapley attributions
-of docs/EXPLAIN.md.
+``explain(X)`` (an oblivious GBDT or a general tree ensemble, with cover, or an MLP / LR with a
+baseline; anything else raises ``ValueError``) returns ``(phi float32/64 [n,30], base_value)``, the
+Shapley attributions of docs/EXPLAIN.md: exact for the trees and LR, sampled for the MLP.
 ``set_drift(reference)`` (oblivious GBDT only, likewise) makes every later ``score(X)`` batch also
 count its rows, binned against the model's table, into a drift window; ``drift()`` reports it
 (docs/DRIFT.md).
@@ -67,6 +67,12 @@ class CpuScorer:
 
     def explain(self, X: np.ndarray) -> Tuple[np.ndarray, float]:
         _explainable(self.model)
+        if self.model.kind == "mlp":
+            from ..models.explain_mlp import shapley_mlp_sampled
+            return shapley_mlp_sampled(self.model, np.asarray(X, np.float32), EXPLAIN_PERMS, EXPLAIN_SEED)
+        if self.model.kind == "lr":
+            from ..models.explain_mlp import shapley_lr
+            return shapley_lr(self.model, np.asarray(X, np.float32))
         if self.model.kind == "forest":
             from ..models.explain_forest import shapley_forest
             return shapley_forest(self.model, np.asarray(X, np.float32))
@@ -74,11 +80,19 @@ class CpuScorer:
         return shapley_oblivious(self.model, np.asarray(X, np.float32))
 
 
+EXPLAIN_PERMS, EXPLAIN_SEED = 64, 0      # the MLP's sampled permutations (docs/EXPLAIN.md)
+
+
 def _explainable(model) -> None:
     kind = getattr(model, "kind", None)
+    if kind in ("mlp", "lr"):
+        if getattr(model, "baseline", None) is None:
+            raise ValueError(f"model kind {kind!r} has no explanation without a baseline row "
+                             "(call fit_baseline(X) first, or train with --explain-baseline)")
+        return
     if kind not in ("gbdt", "forest"):
         raise ValueError(f"model kind {kind!r} has no explanation "
-                         "(exact Shapley values exist for the tree models only)")
+                         "(Shapley values exist for the tree models, and for MLP / LR with a baseline)")
     if kind == "forest" and getattr(model, "cover", None) is None:
         raise ValueError("the ensemble has no cover (background weight of every node): call fit_cover(X) first, "
                          "or import a model that carries one")
@@ -148,13 +162,19 @@ class GpuScorer:
 
     def explain(self, X: np.ndarray) -> Tuple[np.ndarray, float]:
         """csrc/kernels/explain_gbdt.hip (oblivious GBDT) or explain_forest.hip (general trees) on
-        the rows binned against the model's own table."""
+        the rows binned against the model's own table; csrc/kernels/explain_mlp.hip (MLP with a
+        baseline) on the rows as W64; the closed form on the host for LR."""
         _explainable(self.model)
+        if self.model.kind == "lr":
+            from ..models.explain_mlp import shapley_lr
+            return shapley_lr(self.model, np.asarray(X, np.float32))
         with self._lock:
             if self._explainer is None:
                 import torch
-                from ..ops.kernels import DeviceExplainer
-                self._explainer = DeviceExplainer(self.model, device=torch.device("cuda", self._device_index))
+                from ..ops.kernels import DeviceExplainer, DeviceMlpExplainer
+                dev = torch.device("cuda", self._device_index)
+                self._explainer = (DeviceMlpExplainer(self.model, EXPLAIN_PERMS, EXPLAIN_SEED, device=dev)
+                                   if self.model.kind == "mlp" else DeviceExplainer(self.model, device=dev))
             return self._explainer.explain(X)
 
     def close(self):

@@ -75,6 +75,10 @@ def main(argv=None) -> int:
     ap.add_argument("--bits", type=int, default=None, choices=[5, 8],
                     help="--drift-reference-out: bin width of the rows the reference is for (5 = G20, 8 = G32); "
                          "default 5 when the table fits G20 rows, else 8")
+    ap.add_argument("--explain-baseline", default=None, choices=["median", "mean"],
+                    help="MLP / LR: store the per-feature median or mean of the training rows as the model's "
+                         "baseline (fit_baseline), the row its Shapley explanations start from (docs/EXPLAIN.md); "
+                         "off by default")
     ap.add_argument("--metrics-port", type=int, default=0,
                     help="serve the trainer's /metrics (the SparkMetrics dashboard series) on this port "
                          "(+ rank) while training; 0 = off")
@@ -136,6 +140,8 @@ def main(argv=None) -> int:
         raise SystemExit("--bin-spec-from is for --model gbdt")
     if a.drift_reference_out and a.model != "gbdt":
         raise SystemExit("--drift-reference-out is for --model gbdt")
+    if a.explain_baseline and a.model == "gbdt":
+        raise SystemExit("--explain-baseline is for --model mlp|lr (a GBDT is explained through its cover)")
     if a.model == "gbdt":
         spec = None
         if a.bin_spec_from:
@@ -149,6 +155,8 @@ def main(argv=None) -> int:
     else:
         cfg = TrainConfig(epochs=a.epochs, batch=a.batch, device=dev, seed=a.seed, metrics=tm)
         model, info = (train_mlp if a.model == "mlp" else train_logistic)(X[tr], y[tr], cfg)
+        if a.explain_baseline:
+            model = model.fit_baseline(X[tr], a.explain_baseline)
     if rank == 0:
         metrics = evaluate(model, X[te], y[te]) if n_test and 0 < y[te].sum() < n_test else {}
         save_model(model, a.out, version=a.version)

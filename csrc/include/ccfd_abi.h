@@ -271,6 +271,36 @@ int ccfd_forest_explain_launch(const ccfd_forest_explain_args* a, void* stream);
 int64_t ccfd_forest_explain_workspace_bytes(int64_t n, int32_t slices);
 
 // ---------------------------------------------------------------------------
+// Sampled Shapley values of the MLP on W64 rows against one baseline row (explain_mlp.hip;
+// models/explain_mlp.py holds the definition, the CPU oracles and the packer of the 'MLX1'
+// table: header, the baseline as a W64 row, per permutation 32 coalition mask words and the
+// place of every position).  phi[i][j] is the attribution of canonical feature j to the logit of
+// row i; the baseline's logit + sum_j phi[i][j] is the row's logit as this kernel computes it.
+// z_out, when given, receives the logit of every coalition row: slot s of permutation p carries
+// the row's bits on the first s positions of p and the baseline's elsewhere (slots 30, 31: the
+// whole row).  `perms`, `table_head` (the table's first two words: magic, P), `table_bytes` and
+// `blob_bytes` repeat what the caller packed (the launch cannot read device memory): perms even,
+// 2..CCFD_MLX_MAX_PERMS, table_bytes == 128 + 160 * perms, blob_bytes the W64 wire MLP blob's.
+// n >= 0; n == 0 returns without a launch.  A plain grid launch of min(max_workgroups,
+// ceil(n / 4)) workgroups on `stream`.  The sum over permutations has a fixed order that depends
+// on neither n, the grid nor the other rows: a row explained alone gets the bits it gets in a batch.
+#define CCFD_MLX_MAX_PERMS 256
+typedef struct ccfd_mlp_explain_args {
+  const uint8_t* rows;     // device [n][64] W64 rows, 16-byte aligned
+  const void* blob;        // device W64 wire MLP blob, 16-byte aligned
+  const void* table;       // device MLX1 table, 16-byte aligned
+  float* phi;              // device out [n][30], canonical feature order
+  float* z_out;            // device out [n][perms][32] coalition logits, or null
+  int64_t n;
+  int64_t table_bytes;
+  int64_t blob_bytes;
+  int32_t perms;
+  int32_t max_workgroups;  // upper bound on the grid
+  uint32_t table_head[2];  // the table's magic and P, as packed
+} ccfd_mlp_explain_args;   // 80 bytes
+int ccfd_mlp_explain_launch(const ccfd_mlp_explain_args* a, void* stream);
+
+// ---------------------------------------------------------------------------
 // Per-feature bin counts of G32 / G20 rows, for drift detection (drift_hist.hip; models/drift.py
 // holds the definition, the numpy oracle and PSI).  For every row whose stamp equals `stamp`:
 // counts[j][bin_j] += 1 for j < 30, counts[30][amount bucket] += 1 and tail[0] += 1; a row with
