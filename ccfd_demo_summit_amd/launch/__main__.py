@@ -745,7 +745,7 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--drift-reference", default=None,
                     help="seldon/engine/demo: drift reference (train --drift-reference-out) the scored / ingested rows "
                          "are counted against: GET /drift on the Seldon server, ccfd_gpu_drift_* series on the engine "
-                         "(Python ingest, exec_mode launch, G32 / G20 rows)")
+                         "(Python ingest, exec_mode launch; G32 / G20 rows, or W64 rows with an MLP / LR reference)")
     ap.add_argument("--model-metrics-port", type=int, default=None,
                     help="engine: port (+ local rank) of the model's /prometheus (proba_1 / Amount / V17 / V10, "
                          "seldon_api_engine_*); default SELDON port 8000, 0 = off")

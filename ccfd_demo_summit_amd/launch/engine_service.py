@@ -118,17 +118,25 @@ def resolve_exec_mode(exec_mode: str, model_kind: str, row_format: str, input_mo
 def check_drift_tap(drift, dm, exec_mode: str, native_ingest: bool) -> None:
     """Refuse (``ValueError`` naming the reason) every engine a ``DriftMonitor`` cannot tap: the
     tap is the Python ingest path's ``ring_write(tap=)``, over G32 / G20 rows of the reference's
-    own table, beside per-batch launches.  Pure host check."""
+    own table or over W64 rows with a W64 reference, beside per-batch launches.  Pure host check."""
     if native_ingest:
         raise ValueError("drift monitor: the native Kafka consumer writes the rings from C++ and has no tap; "
                          "use the in-process broker or native_ingest=False")
     fmt = dm.row_format
-    if fmt not in ("g32", "g20"):
-        raise ValueError(f"drift monitor: the engine's rows are {fmt}, not binned (G32 / G20: a GBDT packed with bins=)")
+    ref = drift.reference
+    wire_ref = getattr(ref, "is_wire", False)
+    if wire_ref and fmt in ("g32", "g20"):
+        raise ValueError(f"drift monitor: the reference is for W64 rows (quantile bins of the raw values) and the "
+                         f"engine's rows are {fmt}; fit a binned reference against the engine's table (DriftReference.fit)")
+    if fmt not in ("g32", "g20") and not (wire_ref and fmt == "w64"):
+        raise ValueError(f"drift monitor: the engine's rows are {fmt}, not binned (G32 / G20: a GBDT packed with bins=)"
+                         + (", and a W64 reference needs W64 rows (MLP / LR packed with wire=True)" if wire_ref else
+                            "; W64 rows take a W64 reference (DriftReference.fit_wire)" if fmt == "w64" else ""))
     if exec_mode != "launch":
         raise ValueError(f"drift monitor: exec_mode is {exec_mode!r}; a second kernel beside the persistent one is "
                          "not supported, use exec_mode=\"launch\"")
-    ref = drift.reference
+    if wire_ref:
+        return
     if not ref.compatible(dm.bins):
         raise ValueError(f"drift monitor: the reference (stamp {ref.stamp}, {ref.bits}-bit) was not counted against "
                          f"the engine's bin table (stamp {dm.bins.stamp}, {dm.bins.bits}-bit)")

@@ -103,6 +103,14 @@ class DriftHistArgs(C.Structure):        # ccfd_drift_hist_args
                 ("wire", C.c_int32), ("stamp", C.c_int32), ("max_workgroups", C.c_int32), ("pad", C.c_int32)]
 
 
+DRIFT_WIRE_EDGES = 32                    # ccfd_abi.h CCFD_DRIFT_WIRE_EDGES
+
+
+class DriftWireArgs(C.Structure):        # ccfd_drift_wire_args
+    _fields_ = [("rows", C.c_void_p), ("edges", C.c_void_p), ("counts", C.c_void_p), ("tail", C.c_void_p),
+                ("n", C.c_int64), ("max_workgroups", C.c_int32), ("pad", C.c_int32)]
+
+
 class EngineConfig(C.Structure):
     _fields_ = [("device", C.c_int32), ("model", C.c_int32), ("blob", C.c_void_p),
                 ("gbdt_trees", C.c_int32), ("gbdt_depth", C.c_int32), ("threshold", C.c_float),
@@ -188,6 +196,8 @@ def lib() -> C.CDLL:
         L.ccfd_mlp_explain_launch.restype = C.c_int
         L.ccfd_drift_hist_launch.argtypes = [C.POINTER(DriftHistArgs), C.c_void_p]
         L.ccfd_drift_hist_launch.restype = C.c_int
+        L.ccfd_drift_wire_launch.argtypes = [C.POINTER(DriftWireArgs), C.c_void_p]
+        L.ccfd_drift_wire_launch.restype = C.c_int
         L.ccfd_forest_blob_changed.argtypes = [C.c_void_p]
         L.ccfd_forest_blob_changed.restype = None
         L.ccfd_host_alloc.argtypes = [C.c_size_t]

@@ -13,9 +13,9 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from ._lib import (ARG_WIRE_G20, ARG_WIRE_G32, ARG_WIRE_W64, BIN_FORMATS, DRIFT_CELLS, DRIFT_COLS, GBDT_MAX_SPLITS,
-                   MODEL_IDS, N_COUNTER_SLOTS, DriftHistArgs, ForestExplainArgs, GbdtExplainArgs, GbdtHistArgs,
-                   GbdtUpdateArgs, MlpExplainArgs, ScoreArgs, ShadowArgs, check, lib)
+from ._lib import (ARG_WIRE_G20, ARG_WIRE_G32, ARG_WIRE_W64, BIN_FORMATS, DRIFT_CELLS, DRIFT_COLS, DRIFT_WIRE_EDGES,
+                   GBDT_MAX_SPLITS, MODEL_IDS, N_COUNTER_SLOTS, DriftHistArgs, DriftWireArgs, ForestExplainArgs,
+                   GbdtExplainArgs, GbdtHistArgs, GbdtUpdateArgs, MlpExplainArgs, ScoreArgs, ShadowArgs, check, lib)
 
 N_FEATURES = 30
 ROW_BYTES = {"f32": 4 * N_FEATURES, "w64": 64, "g32": 32, "g20": 20}
@@ -527,8 +527,72 @@ def drift_histogram(rows: torch.Tensor, stamp: int, counts: Optional[torch.Tenso
     return counts, tail
 
 
+DRIFT_WIRE_MAX_WORKGROUPS = 1024    # measured: 0.095 ms on 2 M rows against 0.123 ms at 512 (docs/DRIFT.md)
+_wire_tables: dict = {}         # (edge table bytes, device index) -> float32 [30,32] on that device
+
+
+def drift_wire_table(bins, device) -> torch.Tensor:
+    """The ``+inf``-padded float32 ``[30,32]`` edge table of ``bins`` (a wire bin table:
+    ``models.drift.wire_bins``) on ``device``, uploaded once per table and device."""
+    from ..models.drift import wire_edge_table
+    device = torch.device(device)
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    host = wire_edge_table(bins)
+    key = (host.tobytes(), device.index)
+    t = _wire_tables.get(key)
+    if t is None:
+        if len(_wire_tables) >= 16:              # a process holds a handful of tables at most
+            _wire_tables.clear()
+        t = torch.from_numpy(host).to(device)
+        torch.cuda.current_stream(device).synchronize()      # usable from any stream from here on
+        _wire_tables[key] = t
+    return t
+
+
+def _drift_wire_launch(ptr: int, n: int, table: torch.Tensor, counts: torch.Tensor, tail: torch.Tensor,
+                       max_workgroups: int, stream: torch.cuda.Stream) -> None:
+    a = DriftWireArgs()
+    a.rows, a.edges, a.counts, a.tail = ptr, table.data_ptr(), counts.data_ptr(), tail.data_ptr()
+    a.n, a.max_workgroups = int(n), int(max_workgroups)
+    check(lib().ccfd_drift_wire_launch(C.byref(a), C.c_void_p(stream.cuda_stream)), "ccfd_drift_wire_launch")
+
+
+def drift_histogram_wire(rows: torch.Tensor, bins, counts: Optional[torch.Tensor] = None,
+                         tail: Optional[torch.Tensor] = None, max_workgroups: int = DRIFT_WIRE_MAX_WORKGROUPS,
+                         stream: Optional[torch.cuda.Stream] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per-feature quantile-bin counts of W64 rows (csrc/kernels/drift_wire.hip; oracle
+    ``models.drift.wire_bin_counts``).  ``rows``: contiguous CUDA uint8 ``[n,64]``; ``bins``: the wire
+    bin table (a ``BinSpec`` of at most 31 finite edges a feature, e.g. ``wire_bins_fit`` or
+    ``DriftReference.bins``), or its device table from ``drift_wire_table``.  For every row
+    ``counts[j, #{edges_j < x_j}] += 1`` for j < 30 (IEEE float32 compare on the decoded value),
+    ``counts[30, amount bucket] += 1`` and ``tail[0] += 1``; ``tail[1]`` stays as it is (W64 rows
+    carry no stamp).  Outputs, accumulation, exactness and ``max_workgroups`` as
+    ``drift_histogram``, but the default grid bound is 1024: the binning wants more waves a CU.  Rows off a 16-byte boundary are refused by the library."""
+    if not rows.is_cuda or rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != ROW_BYTES["w64"] or \
+            not rows.is_contiguous():
+        raise ValueError("rows must be contiguous CUDA W64 rows ([n,64] u8)")
+    table = bins if isinstance(bins, torch.Tensor) else drift_wire_table(bins, rows.device)
+    if table.device != rows.device or table.dtype != torch.float32 or tuple(table.shape) != (DRIFT_COLS - 1, DRIFT_WIRE_EDGES) \
+            or not table.is_contiguous():
+        raise ValueError("the edge table must be a contiguous float32 [30,32] tensor on the rows' device")
+    if counts is None or tail is None:
+        fresh = new_drift_counts(rows.device)
+        counts = fresh[0] if counts is None else counts
+        tail = fresh[1] if tail is None else tail
+    for name, t, shape in (("counts", counts, (DRIFT_COLS, DRIFT_CELLS)), ("tail", tail, (2,))):
+        if not t.is_cuda or t.device != rows.device or t.dtype != torch.uint64 or tuple(t.shape) != shape or \
+                not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous CUDA uint64 tensor of shape {list(shape)} on the rows' device")
+    s = stream if stream is not None else torch.cuda.current_stream(rows.device)
+    _drift_wire_launch(rows.data_ptr(), rows.shape[0], table, counts, tail, max_workgroups, s)
+    return counts, tail
+
+
 class DriftMonitor:
-    """A tumbling window of bin counts on the GPU, compared against a ``models.drift.DriftReference``.
+    """A tumbling window of bin counts on the GPU, compared against a ``models.drift.DriftReference``
+    (G32 / G20 rows of a binned reference, or W64 rows of a ``fit_wire`` one, whose padded edge
+    table the monitor holds on its device).
 
     ``observe(rows)`` counts CUDA rows on the caller's current stream; ``observe_host(rows)``
     copies a host ``uint8 [k, row_bytes]`` view into one of two pinned staging buffers and counts
@@ -536,17 +600,23 @@ class DriftMonitor:
     the engines read their logs), so the caller's memory is free again when it returns.
     ``report()`` reads the counts back and computes PSI on the host.  Thread-safe (one lock)."""
 
-    def __init__(self, reference, device: torch.device | str | int = "cuda", max_workgroups: int = 512,
+    def __init__(self, reference, device: torch.device | str | int = "cuda", max_workgroups: Optional[int] = None,
                  min_rows: int = 10_000, bands=(0.1, 0.25)):
+        """``max_workgroups``: the launches' grid bound; ``None`` is each kernel's default (512 for
+        binned rows, 1024 for W64 rows)."""
         from ..engine.stream_engine import PinnedArray
         self.reference = reference
-        self.fmt = "g32" if reference.bits == 8 else "g20"
+        wire = getattr(reference, "is_wire", False)
+        self.fmt = "w64" if wire else "g32" if reference.bits == 8 else "g20"
         self.row_bytes = ROW_BYTES[self.fmt]
         self.device = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
+        if max_workgroups is None:
+            max_workgroups = DRIFT_WIRE_MAX_WORKGROUPS if wire else 512
         self.max_workgroups, self.min_rows, self.bands = int(max_workgroups), int(min_rows), tuple(bands)
         self.counts, self.tail = new_drift_counts(self.device)
+        self._table = drift_wire_table(reference.bins, self.device) if wire else None    # W64: the padded edges
         with torch.cuda.device(self.device):
             self._stream = torch.cuda.Stream(self.device)
             self._stage = [PinnedArray((DRIFT_STAGE_ROWS, self.row_bytes), np.uint8) for _ in range(2)]
@@ -568,7 +638,10 @@ class DriftMonitor:
         self._check(rows.shape[1])
         with self._lock:
             s = torch.cuda.current_stream(self.device)
-            drift_histogram(rows, self.reference.stamp, self.counts, self.tail, self.max_workgroups, s)
+            if self._table is not None:
+                drift_histogram_wire(rows, self._table, self.counts, self.tail, self.max_workgroups, s)
+            else:
+                drift_histogram(rows, self.reference.stamp, self.counts, self.tail, self.max_workgroups, s)
             self._streams[s.cuda_stream] = s
 
     def observe_host(self, rows: np.ndarray) -> None:
@@ -585,8 +658,12 @@ class DriftMonitor:
                     self._busy[b].synchronize()          # the launch that read this buffer last
                 k = chunk.shape[0]
                 self._stage[b].array[:k] = chunk
-                _drift_launch(self._stage_ptr[b], k, self.fmt, self.reference.stamp, self.counts, self.tail,
-                              self.max_workgroups, self._stream)
+                if self._table is not None:
+                    _drift_wire_launch(self._stage_ptr[b], k, self._table, self.counts, self.tail,
+                                       self.max_workgroups, self._stream)
+                else:
+                    _drift_launch(self._stage_ptr[b], k, self.fmt, self.reference.stamp, self.counts, self.tail,
+                                  self.max_workgroups, self._stream)
                 ev = torch.cuda.Event()
                 ev.record(self._stream)
                 self._busy[b] = ev

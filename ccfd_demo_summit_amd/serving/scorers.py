@@ -8,9 +8,10 @@ Both return ``(proba_1 float32[n], route uint8[n])`` with route = proba >= thres
 ``explain(X)`` (an oblivious GBDT or a general tree ensemble, with cover, or an MLP / LR with a
 baseline; anything else raises ``ValueError``) returns ``(phi float32/64 [n,30], base_value)``, the
 Shapley attributions of docs/EXPLAIN.md: exact for the trees and LR, sampled for the MLP.
-``set_drift(reference)`` (oblivious GBDT only, likewise) makes every later ``score(X)`` batch also
-count its rows, binned against the model's table, into a drift window; ``drift()`` reports it
-(docs/DRIFT.md).
+``set_drift(reference)`` makes every later ``score(X)`` batch also count its rows into a drift
+window -- binned against the model's table for an oblivious GBDT with a binned reference, as W64
+rows against the reference's own quantile table for an MLP / LR with a W64 reference; any other
+pairing raises ``ValueError`` -- and ``drift()`` reports it (docs/DRIFT.md).
 """
 from __future__ import annotations
 
@@ -19,6 +20,8 @@ from typing import Tuple
 
 import numpy as np
 
+from ..contracts.transaction import encode_wire
+
 
 class CpuScorer:
     device = "cpu"
@@ -26,7 +29,7 @@ class CpuScorer:
     def __init__(self, model, threshold: float = 0.5):
         self.model = model
         self.threshold = float(threshold)
-        self._drift = None           # (reference, bins, counts, tail) after set_drift
+        self._drift = None           # (reference, bins or None for W64, counts, tail) after set_drift
         self._drift_min_rows = 10_000
         self._drift_lock = threading.Lock()
 
@@ -34,10 +37,12 @@ class CpuScorer:
         X = np.asarray(X, np.float32)
         p = self.model.predict_proba(X).astype(np.float32)
         if self._drift is not None:
-            from ..models.drift import bin_counts
+            from ..models.drift import bin_counts, wire_bin_counts
             with self._drift_lock:
                 ref, bins, counts, tail = self._drift
-                c, t = bin_counts(bins.encode(X.reshape(-1, X.shape[-1])), ref.stamp)
+                rows = X.reshape(-1, X.shape[-1])
+                c, t = wire_bin_counts(encode_wire(rows), ref.edges) if bins is None else \
+                    bin_counts(bins.encode(rows), ref.stamp)
                 counts += c
                 tail += t
         return p, (p >= self.threshold).astype(np.uint8)
@@ -99,11 +104,19 @@ def _explainable(model) -> None:
 
 
 def _drift_bins(model, reference):
-    """The model's own bin table at the reference's width, refused unless the reference was
-    counted against it."""
-    if getattr(model, "kind", None) != "gbdt":
-        raise ValueError(f"model kind {getattr(model, 'kind', None)!r} has no drift detector "
-                         "(bin counts exist for the oblivious GBDT's split table only)")
+    """The model's own bin table at a binned reference's width, refused unless the reference was
+    counted against it; ``None`` for a W64 reference on an MLP / LR, whose rows are counted as
+    W64 against the reference's own table."""
+    kind = getattr(model, "kind", None)
+    if getattr(reference, "is_wire", False):
+        if kind not in ("mlp", "lr"):
+            raise ValueError(f"drift reference is for W64 rows (quantile bins of the raw values), which model kind "
+                             f"{kind!r} does not score; fit a binned reference against its table (DriftReference.fit)")
+        return None
+    if kind != "gbdt":
+        raise ValueError(f"model kind {kind!r} has no drift detector for a binned reference "
+                         "(bin counts exist for the oblivious GBDT's split table only; an MLP / LR takes a "
+                         "W64 reference, DriftReference.fit_wire)")
     bins = model.bin_spec(bits=reference.bits)
     if not reference.compatible(bins):
         raise ValueError(f"drift reference (stamp {reference.stamp}, {reference.bits}-bit) was not counted against "
@@ -123,7 +136,7 @@ class GpuScorer:
         self.model = model
         self._device_index = device_index
         self._explainer = None
-        self._drift = None           # (DriftMonitor, bins) after set_drift
+        self._drift = None           # (DriftMonitor, bins or None for W64) after set_drift
         self.dm = DeviceModel(model, torch.device("cuda", device_index))
         self.engine = StreamEngine(self.dm, batch=max_batch, depth=depth, streams=1,
                                    input_mode="dma", output_mode="zerocopy", threshold=threshold,
@@ -136,13 +149,14 @@ class GpuScorer:
                 import torch
                 mon, bins = self._drift
                 X = np.asarray(X, np.float32)
-                rows = np.ascontiguousarray(bins.encode(X.reshape(-1, X.shape[-1])))
+                rows = X.reshape(-1, X.shape[-1])
+                rows = np.ascontiguousarray(encode_wire(rows) if bins is None else bins.encode(rows))
                 mon.observe(torch.from_numpy(rows).to(mon.device))
             return self.engine.score(X)
 
     def set_drift(self, reference, min_rows: int = 10_000) -> None:
         """Count every later ``score`` batch against ``reference`` with
-        csrc/kernels/drift_hist.hip (``None`` turns it off)."""
+        csrc/kernels/drift_hist.hip, or drift_wire.hip for a W64 reference (``None`` turns it off)."""
         with self._lock:
             if self._drift is not None:
                 self._drift[0].close()

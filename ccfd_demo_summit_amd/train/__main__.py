@@ -70,11 +70,14 @@ def main(argv=None) -> int:
                          "trained ensemble packs against the table the live G32 / G20 logs were encoded with "
                          "(a challenger for `launch engine --shadow-model`); replaces --max-borders")
     ap.add_argument("--drift-reference-out", default=None, metavar="REF.safetensors",
-                    help="GBDT: also write the drift reference of the training rows against the trained model's "
-                         "bin table (models/drift.py; `launch seldon|engine --drift-reference`)")
+                    help="also write the drift reference of the training rows (models/drift.py; `launch "
+                         "seldon|engine --drift-reference`): against the trained model's bin table for a GBDT, "
+                         "as W64 rows against their own quantile table (--drift-cells) for an MLP / LR")
     ap.add_argument("--bits", type=int, default=None, choices=[5, 8],
-                    help="--drift-reference-out: bin width of the rows the reference is for (5 = G20, 8 = G32); "
-                         "default 5 when the table fits G20 rows, else 8")
+                    help="GBDT --drift-reference-out: bin width of the rows the reference is for (5 = G20, "
+                         "8 = G32); default 5 when the table fits G20 rows, else 8")
+    ap.add_argument("--drift-cells", type=int, default=32, metavar="N",
+                    help="MLP / LR --drift-reference-out: quantile cells per feature of the W64 reference, 2..32")
     ap.add_argument("--explain-baseline", default=None, choices=["median", "mean"],
                     help="MLP / LR: store the per-feature median or mean of the training rows as the model's "
                          "baseline (fit_baseline), the row its Shapley explanations start from (docs/EXPLAIN.md); "
@@ -138,8 +141,12 @@ def main(argv=None) -> int:
         dev = f"cuda:{torch.cuda.current_device()}"
     if a.bin_spec_from and a.model != "gbdt":
         raise SystemExit("--bin-spec-from is for --model gbdt")
-    if a.drift_reference_out and a.model != "gbdt":
-        raise SystemExit("--drift-reference-out is for --model gbdt")
+    if a.drift_reference_out and a.model not in ("gbdt", "mlp", "lr"):
+        raise SystemExit("--drift-reference-out is for --model gbdt|mlp|lr")
+    if a.bits is not None and a.model != "gbdt":
+        raise SystemExit("--bits is for --model gbdt (an MLP / LR reference is for W64 rows: --drift-cells)")
+    if not 2 <= a.drift_cells <= 32:
+        raise SystemExit("--drift-cells is 2..32")
     if a.explain_baseline and a.model == "gbdt":
         raise SystemExit("--explain-baseline is for --model mlp|lr (a GBDT is explained through its cover)")
     if a.model == "gbdt":
@@ -163,10 +170,14 @@ def main(argv=None) -> int:
         out = {"model": a.model, "out": a.out, "world": world, "train": info, "holdout": metrics}
         if a.drift_reference_out:
             from ..models.drift import DriftReference
-            bits = a.bits or (5 if model.bin_spec().fits_g20 else 8)
-            ref = DriftReference.fit(X[tr], model.bin_spec(bits=bits))
+            if a.model == "gbdt":
+                bits = a.bits or (5 if model.bin_spec().fits_g20 else 8)
+                ref = DriftReference.fit(X[tr], model.bin_spec(bits=bits))
+            else:
+                ref = DriftReference.fit_wire(X[tr], cells=a.drift_cells)
             ref.save(a.drift_reference_out)
-            out["drift_reference"] = {"out": a.drift_reference_out, "bits": bits, "stamp": ref.stamp, "rows": ref.rows}
+            out["drift_reference"] = {"out": a.drift_reference_out, "bits": ref.bits, "stamp": ref.stamp,
+                                      "rows": ref.rows}
         print(json.dumps(out, default=float), flush=True)
     if world > 1:
         dist.barrier()

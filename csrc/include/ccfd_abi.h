@@ -324,6 +324,27 @@ typedef struct ccfd_drift_hist_args {
 } ccfd_drift_hist_args;   // 48 bytes
 int ccfd_drift_hist_launch(const ccfd_drift_hist_args* a, void* stream);
 
+// The same counts for W64 rows, which carry values and no bins (drift_wire.hip; oracle
+// models/drift.py wire_bin_counts).  The kernel bins each of the 30 features, in canonical order
+// (Time, V1..V28, Amount), against `edges`: counts[j][#{edges_j < x_j}] += 1 with the IEEE f32
+// compare on the decoded value (NaN -> cell 0, denormals kept), counts[30][amount bucket] += 1,
+// tail[0] += 1.  W64 rows carry no stamp: tail[1] is never touched.  `edges` is
+// float[30][CCFD_DRIFT_WIRE_EDGES]: a feature's <= 31 ascending edges followed by +inf, which is
+// below no value, so the padding never counts.  Only cells 0..31 of a column are reached.
+// Accumulates, n == 0 returns without a launch, max_workgroups >= 1, and the grid is
+// min(max_workgroups, ceil(n / 1024)) workgroups, all as ccfd_drift_hist_launch.
+#define CCFD_DRIFT_WIRE_EDGES 32
+typedef struct ccfd_drift_wire_args {
+  const uint8_t* rows;          // device-visible [n][64], 16-byte aligned
+  const float* edges;           // device [30][32], +inf padded
+  unsigned long long* counts;   // device [31][256], accumulated
+  unsigned long long* tail;     // device [2] = {rows counted, 0}, accumulated
+  int64_t n;
+  int32_t max_workgroups;       // upper bound on the grid
+  int32_t pad;
+} ccfd_drift_wire_args;   // 48 bytes
+int ccfd_drift_wire_launch(const ccfd_drift_wire_args* a, void* stream);
+
 // ---------------------------------------------------------------------------
 // Persistent streaming kernel (exec_mode = 1): ONE long-running launch per engine; the
 // host publishes micro-batch descriptors into a ring in coherent pinned memory and bumps

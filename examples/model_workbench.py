@@ -136,6 +136,15 @@ def main(argv=None) -> dict:
     drift = DriftReport.compare(ref, *bin_counts(rows, spec.stamp))
     report["drift"] = {"rows": drift.rows, "worst": [{"feature": n, "psi": v, "status": s} for n, v, s in drift.worst(3)]}
     print("drift train -> holdout, worst PSI: " + ", ".join(f"{n} {v:.4f} ({s})" for n, v, s in drift.worst(3)))
+    # the MLP / LR see W64 rows and have no table: the reference brings 32 quantile cells a feature
+    from ccfd_demo_summit_amd.contracts.transaction import encode_wire
+    from ccfd_demo_summit_amd.models.drift import wire_bin_counts
+    wref = DriftReference.fit_wire(Xtr)
+    wdrift = DriftReport.compare(wref, *wire_bin_counts(encode_wire(Xte), wref.edges))
+    report["drift_w64"] = {"rows": wdrift.rows,
+                           "worst": [{"feature": n, "psi": v, "status": s} for n, v, s in wdrift.worst(3)]}
+    print("drift train -> holdout on W64 rows (MLP / LR), worst PSI: "
+          + ", ".join(f"{n} {v:.4f} ({s})" for n, v, s in wdrift.worst(3)))
 
     # %% score through the MI355X kernels
     if torch.cuda.is_available() and device.startswith("cuda"):
