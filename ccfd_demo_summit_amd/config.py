@@ -101,6 +101,8 @@ class EngineConfig:
     shadow_model: str = ""           # challenger (safetensors MLP, or GBDT on binned rows) scored beside the live model, counters only
     drift_reference: str = ""        # drift reference (safetensors, train --drift-reference-out): every ingested row is
                                      # counted against it, ccfd_gpu_drift_* series (Python ingest, launch mode, G32 / G20)
+    outlier_model: str = ""          # outlier autoencoder (safetensors, train --outlier-out): every ingested W64 row is
+                                     # scored by it, ccfd_gpu_outlier_* series (Python ingest, launch mode, W64 rows)
     output_mode: str = "zerocopy"    # zerocopy (kernel writes pinned host) | dma
     exec_mode: str = "auto"          # persistent | launch | auto (persistent for zero-copy in/out:
                                      # the mode bench.py measures; launch_/engine_service.py)
@@ -157,6 +159,7 @@ ENV_MAP = {
     "CCFD_MODEL_WATCH": ("engine", "model_watch", str),
     "CCFD_SHADOW_MODEL": ("engine", "shadow_model", str),
     "CCFD_DRIFT_REFERENCE": ("engine", "drift_reference", str),
+    "CCFD_OUTLIER_MODEL": ("engine", "outlier_model", str),
     "CCFD_INPUT_MODE": ("engine", "input_mode", str),
     "CCFD_OUTPUT_MODE": ("engine", "output_mode", str),
     "CCFD_EXEC_MODE": ("engine", "exec_mode", str),

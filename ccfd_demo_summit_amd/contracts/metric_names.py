@@ -43,6 +43,13 @@ GPU_DRIFT_PSI = GPU_PREFIX + "drift_psi"             # gauge{feature}: PSI of th
 GPU_DRIFT_ROWS = GPU_PREFIX + "drift_rows"           # counter (_total): rows counted in the window
 GPU_DRIFT_STALE_ROWS = GPU_PREFIX + "drift_stale_rows"    # counter (_total): rows of another bin table
 GPU_DRIFT_FEATURES_DRIFTING = GPU_PREFIX + "drift_features_drifting"   # gauge: columns with status "drift"
+# autoencoder outlier scores of the ingested rows (docs/OUTLIER.md); all of the open window
+GPU_OUTLIER_ROWS = GPU_PREFIX + "outlier_rows"                   # counter (_total): rows scored
+GPU_OUTLIER_FLAGGED = GPU_PREFIX + "outlier_flagged"             # counter (_total): score > threshold
+GPU_OUTLIER_INVALID_ROWS = GPU_PREFIX + "outlier_invalid_rows"   # counter (_total): non-finite score
+GPU_OUTLIER_RATE = GPU_PREFIX + "outlier_rate"                   # gauge: flagged / rows with a finite score
+GPU_OUTLIER_SCORE_BUCKET = GPU_PREFIX + "outlier_score_bucket"   # gauge{le}: cumulative score cells, le = 2^(k-15)
+GPU_OUTLIER_TOP_FEATURE = GPU_PREFIX + "outlier_top_feature"     # gauge (_total){feature}: flagged rows by worst feature
 
 ROUTER_METRICS = (TRANSACTION_INCOMING, TRANSACTION_OUTGOING, NOTIFICATIONS_OUTGOING,
                   NOTIFICATIONS_INCOMING)

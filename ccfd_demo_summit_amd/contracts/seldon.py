@@ -100,6 +100,41 @@ def build_explain_response(phi, base_value: float, proba1, model_name: str = "mo
     return {"meta": meta, "data": {"names": list(FEATURE_NAMES), "ndarray": phi.tolist()}}
 
 
+def _json_float(v):
+    v = float(v)
+    return v if v == v and abs(v) != float("inf") else None
+
+
+def build_outlier_response(score, is_outlier, sq_err, threshold: float, model_name: str = "modelfull",
+                           top: int = 3) -> dict:
+    """Outlier route: one ``[score, is_outlier]`` row per input row (Seldon data format, the
+    outlier-detector convention), and in ``meta.tags`` the threshold and, per row, the ``top``
+    features by squared reconstruction error.  A non-finite score (a row with a non-finite
+    feature) is ``null`` and never an outlier."""
+    score = np.asarray(score, np.float32).reshape(-1)
+    flag = np.asarray(is_outlier, bool).reshape(-1)
+    sq = np.asarray(sq_err, np.float32).reshape(-1, N_FEATURES)
+    order = np.argsort(-np.nan_to_num(sq, nan=-1.0), axis=1, kind="stable")[:, :top]
+    tops = [[{"name": FEATURE_NAMES[j], "sq_err": _json_float(sq[i, j])} for j in row.tolist()]
+            for i, row in enumerate(order)]
+    meta = {"puid": uuid.uuid4().hex, "routing": {}, "requestPath": {model_name: model_name},
+            "tags": {"threshold": _json_float(threshold), "top_features": tops}}
+    return {"meta": meta, "data": {"names": ["score", "is_outlier"],
+                                   "ndarray": [[_json_float(s), int(f)] for s, f in zip(score.tolist(), flag.tolist())]}}
+
+
+def parse_outlier_response(body) -> Tuple[np.ndarray, np.ndarray, float, list]:
+    """``(score float32 [n] (NaN for null), is_outlier bool [n], threshold, top_features)``."""
+    if isinstance(body, (bytes, bytearray, str)):
+        body = json.loads(body)
+    rows = body["data"]["ndarray"]
+    score = np.array([np.nan if r[0] is None else r[0] for r in rows], np.float32)
+    tags = body["meta"]["tags"]
+    thr = tags["threshold"]
+    return score, np.array([bool(r[1]) for r in rows], bool), float("inf") if thr is None else float(thr), \
+        tags["top_features"]
+
+
 def parse_response(body) -> Tuple[np.ndarray, list]:
     if isinstance(body, (bytes, bytearray, str)):
         body = json.loads(body)

@@ -185,12 +185,22 @@ def _set_drift(scorer, a) -> None:
         print(f"[drift] reference {path}: GET /drift reports PSI per feature", flush=True)
 
 
+def _set_outlier(scorer, a) -> None:
+    """--outlier-model: score every batch with the autoencoder too (the /outlier routes)."""
+    path = getattr(a, "outlier_model", None)
+    if path:
+        from ..models import load_model
+        scorer.set_outlier(load_model(path))
+        print(f"[outlier] model {path}: POST /outlier scores rows, GET /outlier reports the window", flush=True)
+
+
 def cmd_seldon(a, cfg):
     from ..serving.scorers import make_scorer
     from ..serving.seldon_server import SeldonServer, run
     model = _model(cfg.engine.model, a.weights, cfg.seed)
     scorer = make_scorer(model, cfg.router.fraud_threshold, device=a.device, max_batch=cfg.seldon.max_batch)
     _set_drift(scorer, a)
+    _set_outlier(scorer, a)
     if a.native:
         # C++ epoll front end (csrc/engine/seldon_http.cpp): same routes, JSON and metrics
         from ..serving.native_seldon import NativeSeldonServer
@@ -384,7 +394,8 @@ def engine_service_settings(a, cfg):
         native_serve=cfg.engine.native_serve,
         model_watch=(a.watch_model or cfg.engine.model_watch or None),
         shadow_model=(a.shadow_model or cfg.engine.shadow_model or None),
-        drift_reference=(getattr(a, "drift_reference", None) or cfg.engine.drift_reference or None))
+        drift_reference=(getattr(a, "drift_reference", None) or cfg.engine.drift_reference or None),
+        outlier_model=(getattr(a, "outlier_model", None) or cfg.engine.outlier_model or None))
 
 
 def cmd_engine(a, cfg):
@@ -445,7 +456,13 @@ def cmd_engine(a, cfg):
         from ..ops.kernels import DriftMonitor
         drift = DriftMonitor(DriftReference.load(settings.drift_reference), ctx.device)
         print(f"[engine] drift reference {settings.drift_reference}: ccfd_gpu_drift_* series", flush=True)
-    svc = EngineService(ctx, dm, broker, router, settings, shadow=shadow, drift=drift).start()
+    outlier = None
+    if settings.outlier_model:
+        from ..models import load_model
+        from ..ops.kernels import OutlierMonitor
+        outlier = OutlierMonitor(load_model(settings.outlier_model), ctx.device)
+        print(f"[engine] outlier model {settings.outlier_model}: ccfd_gpu_outlier_* series", flush=True)
+    svc = EngineService(ctx, dm, broker, router, settings, shadow=shadow, drift=drift, outlier=outlier).start()
     hub.gpu_registry.register(GpuEngineCollector(svc.metrics_source, rank_label=str(ctx.rank)))
     # the process's node-local rank (torchrun LOCAL_RANK) -- not the device index, which a
     # several-ranks-per-GPU rehearsal (CCFD_DEVICE_MODULO) maps onto the same GPU
@@ -565,6 +582,7 @@ def cmd_demo(a, cfg):
     model = _model(cfg.engine.model, a.weights, cfg.seed)
     scorer = make_scorer(model, cfg.router.fraud_threshold, device=a.device)
     _set_drift(scorer, a)
+    _set_outlier(scorer, a)
     pipe = FraudPipeline(cfg, scorer, InProcBroker(default_partitions=cfg.kafka.partitions))
     _serve_in_thread(_metrics_app(pipe.metrics.expose_all), a.host, a.port or cfg.router.port)
     prod = TransactionProducer(pipe.broker, ProducerConfig(fmt=a.fmt, batch=a.batch, rate_tx_s=a.rate))
@@ -577,6 +595,8 @@ def cmd_demo(a, cfg):
     out = {"consumed": pipe.stats.consumed, "outcomes": oc, "scorer": getattr(scorer, "device", "cpu")}
     if getattr(a, "drift_reference", None):
         out["drift"] = scorer.drift().to_json()
+    if getattr(a, "outlier_model", None):
+        out["outlier"] = scorer.outlier_report().to_json()
     print(json.dumps(out), flush=True)
 
 
@@ -746,6 +766,10 @@ def parse_args(argv=None) -> argparse.Namespace:
                     help="seldon/engine/demo: drift reference (train --drift-reference-out) the scored / ingested rows "
                          "are counted against: GET /drift on the Seldon server, ccfd_gpu_drift_* series on the engine "
                          "(Python ingest, exec_mode launch; G32 / G20 rows, or W64 rows with an MLP / LR reference)")
+    ap.add_argument("--outlier-model", default=None,
+                    help="seldon/engine/demo: outlier autoencoder (train --outlier-out) run beside the fraud model: "
+                         "POST / GET /outlier on the Seldon server, ccfd_gpu_outlier_* series on the engine "
+                         "(Python ingest, exec_mode launch, W64 rows)")
     ap.add_argument("--model-metrics-port", type=int, default=None,
                     help="engine: port (+ local rank) of the model's /prometheus (proba_1 / Amount / V17 / V10, "
                          "seldon_api_engine_*); default SELDON port 8000, 0 = off")

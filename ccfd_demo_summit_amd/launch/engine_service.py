@@ -77,6 +77,8 @@ class EngineServiceConfig:
     model_watch: Optional[str] = None   # rank 0: hot-swap when this safetensors file changes
     drift_reference: Optional[str] = None  # file the drift reference was loaded from; the monitor
                                            # itself is EngineService(drift=)
+    outlier_model: Optional[str] = None    # file the outlier autoencoder was loaded from; the monitor
+                                           # itself is EngineService(outlier=)
     shadow_model: Optional[str] = None  # file the shadow (challenger) model was loaded from; the
                                         # packed model itself is EngineService(shadow=)
     handoff_hold_low: float = 0.5    # a held (full) hand-off queue resumes scoring below this fill
@@ -142,15 +144,49 @@ def check_drift_tap(drift, dm, exec_mode: str, native_ingest: bool) -> None:
                          f"the engine's bin table (stamp {dm.bins.stamp}, {dm.bins.bits}-bit)")
 
 
+def check_outlier_tap(outlier, dm, exec_mode: str, native_ingest: bool) -> None:
+    """Refuse (``ValueError`` naming the reason) every engine an ``OutlierMonitor`` cannot tap: the
+    tap is the Python ingest path's ``ring_write(tap=)``, over W64 rows, beside per-batch launches.
+    Pure host check."""
+    if native_ingest:
+        raise ValueError("outlier monitor: the native Kafka consumer writes the rings from C++ and has no tap; "
+                         "use the in-process broker or native_ingest=False")
+    fmt = dm.row_format
+    if fmt != "w64":
+        raise ValueError(f"outlier monitor: the engine's rows are {fmt}; the autoencoder scores W64 rows "
+                         "(MLP / LR packed with wire=True)")
+    if exec_mode != "launch":
+        raise ValueError(f"outlier monitor: exec_mode is {exec_mode!r}; a second kernel beside the persistent one is "
+                         "not supported, use exec_mode=\"launch\"")
+
+
+def outlier_series(rep) -> dict:
+    """The ``ccfd_gpu_outlier_*`` series of an ``OutlierReport`` as ``metrics_source`` extras, all of
+    the open window: three counters, the rate, the 32 score cells as a cumulative
+    ``ccfd_gpu_outlier_score_bucket{le}`` gauge (``le`` = the cell's upper bound 2^(k-15), then
+    ``+Inf``; a gauge because a window reset takes it back to 0) and
+    ``ccfd_gpu_outlier_top_feature_total{feature}``."""
+    cut = len(M.GPU_PREFIX)                  # gauges get the prefix back in the collector
+    cum = np.cumsum(rep.histogram)
+    le = {repr(float(2.0 ** (k - 15))): int(cum[k]) for k in range(31)}
+    le["+Inf"] = int(cum[31])
+    return {M.GPU_OUTLIER_ROWS + "_total": rep.rows, M.GPU_OUTLIER_FLAGGED + "_total": rep.outliers,
+            M.GPU_OUTLIER_INVALID_ROWS + "_total": rep.invalid, M.GPU_OUTLIER_RATE[cut:]: rep.outlier_rate,
+            M.GPU_OUTLIER_SCORE_BUCKET[cut:]: {"le": le},
+            (M.GPU_OUTLIER_TOP_FEATURE + "_total")[cut:]: {"feature": dict(zip(rep.names, rep.top_feature.tolist()))}}
+
+
 class EngineService:
     def __init__(self, ctx, dm, broker, router, cfg: EngineServiceConfig, reducer=None, partitions=None,
-                 shadow=None, drift=None):
+                 shadow=None, drift=None, outlier=None):
         """``shadow``: a challenger DeviceModel (an MLP on W64 rows, or a GBDT of ``dm``'s shape
         packed against ``dm``'s G32 / G20 bin table) scored beside ``dm`` from the
         first micro-batch on; its results are the shadow counter slots of the X2 all-reduce and
         the ``ccfd_gpu_shadow_*`` series (engine.StreamEngine.set_shadow).
         ``drift``: an ``ops.kernels.DriftMonitor`` fed every ingested row (``ring_write(tap=)``)
-        and reported as the ``ccfd_gpu_drift_*`` series; ``check_drift_tap`` lists what is refused."""
+        and reported as the ``ccfd_gpu_drift_*`` series; ``check_drift_tap`` lists what is refused.
+        ``outlier``: an ``ops.kernels.OutlierMonitor`` fed from the same tap (with both set, one tap
+        calls both) and reported as the ``ccfd_gpu_outlier_*`` series; ``check_outlier_tap``."""
         from ..engine import StreamEngine
         from ..parallel.dp import CounterReducer, EpochPipeline, assign_partitions, x_group
         self.ctx = ctx
@@ -177,6 +213,17 @@ class EngineService:
         if drift is not None:
             check_drift_tap(drift, dm, self.exec_mode, bool(cfg.native_ingest and hasattr(broker, "_bootstrap")))
             self._tap = drift.observe_host
+        self.outlier = outlier
+        self._outlier_report = None
+        if outlier is not None:
+            check_outlier_tap(outlier, dm, self.exec_mode, bool(cfg.native_ingest and hasattr(broker, "_bootstrap")))
+            if drift is not None:
+                def _both(rows, _a=drift.observe_host, _b=outlier.observe_host):
+                    _a(rows)
+                    _b(rows)
+                self._tap = _both
+            else:
+                self._tap = outlier.observe_host
         self.engine = StreamEngine(dm, batch=cfg.batch, depth=cfg.depth, streams=cfg.streams,
                                    input_mode=cfg.input_mode, output_mode=cfg.output_mode, threshold=threshold,
                                    device=ctx.device.index, exec_mode=self.exec_mode, coalesce=cfg.coalesce,
@@ -526,6 +573,8 @@ class EngineService:
         """Read the drift window back (epoch cadence, never per batch) for ``metrics_source``."""
         if self.drift is not None:
             self._drift_report = self.drift.report()
+        if self.outlier is not None:
+            self._outlier_report = self.outlier.report()
 
     def _score_loop(self) -> None:
         try:
@@ -765,6 +814,8 @@ class EngineService:
                 cut = len(M.GPU_PREFIX)                  # gauges get the prefix back in the collector
                 extra[M.GPU_DRIFT_PSI[cut:]] = {"feature": dict(zip(rep.names, rep.psi.tolist()))}
                 extra[M.GPU_DRIFT_FEATURES_DRIFTING[cut:]] = rep.drifting
+        if self._outlier_report is not None:
+            extra.update(outlier_series(self._outlier_report))
         if self.standard_mode == "process":
             extra.update(standard_started=getattr(self.router, "standard_started", 0))
         with self._stat_lock:

@@ -16,10 +16,12 @@ from .forest import TreeEnsemble
 from .gbdt import ObliviousGBDT
 from .lr import LogisticModel
 from .mlp import MLPModel
+from .outlier import OutlierAE
 from .usertask import UserTaskModel
 
 AnyModel = Union[LogisticModel, MLPModel, ObliviousGBDT, TreeEnsemble]
-KINDS = {"lr": LogisticModel, "mlp": MLPModel, "gbdt": ObliviousGBDT, "forest": TreeEnsemble}
+# "ae" is the outlier autoencoder (models/outlier.py): saved and loaded like the others, but no fraud scorer
+KINDS = {"lr": LogisticModel, "mlp": MLPModel, "gbdt": ObliviousGBDT, "forest": TreeEnsemble, "ae": OutlierAE}
 
 
 def build_model(kind: str, seed: int = 0, X_ref=None, calibrate_rate=None, threshold: float = 0.5,
@@ -58,5 +60,5 @@ def load_model(path: str) -> AnyModel:
     return KINDS[kind].from_state_dict(st)
 
 
-__all__ = ["Normalizer", "LogisticModel", "MLPModel", "ObliviousGBDT", "TreeEnsemble", "UserTaskModel",
+__all__ = ["Normalizer", "LogisticModel", "MLPModel", "ObliviousGBDT", "TreeEnsemble", "UserTaskModel", "OutlierAE",
            "build_model", "save_model", "load_model", "KINDS", "bf16_round", "sigmoid"]

@@ -69,6 +69,39 @@ def _pi(s: int, g: int, j: int) -> int:
     return 32 * s + 4 * g + (j & 3) + 16 * (j >> 2)
 
 
+def wire_layer1(W1: np.ndarray, b1: np.ndarray, norm: Normalizer) -> np.ndarray:
+    """Layer-1 matrix [H, 32] of a wire blob from ``W1 [H,30]`` / ``b1 [H]`` (wire K order; the
+    V-normalisation folded into the columns, the bias as a bf16 hi/lo pair in columns 30 / 31),
+    as float32 before bf16 rounding.  Shared by the MLP and the outlier autoencoder."""
+    W1p = np.zeros((W1.shape[0], KPAD), np.float32)
+    W1w = W1[:, WIRE_PERM].astype(np.float64)
+    mu = norm.mu[WIRE_PERM].astype(np.float64)
+    isg = norm.inv_sigma[WIRE_PERM].astype(np.float64)
+    v = np.arange(N_FEATURES) < WIRE_N_BF16
+    W1w[:, v] *= isg[v]
+    b1w = b1.astype(np.float64) - W1w[:, v] @ mu[v]
+    W1p[:, :N_FEATURES] = W1w
+    hi = bf16_round(b1w.astype(np.float32))
+    W1p[:, N_FEATURES] = hi
+    W1p[:, N_FEATURES + 1] = bf16_round((b1w - hi).astype(np.float32))
+    return W1p
+
+
+def wire_operands(norm: Normalizer, Xd: np.ndarray) -> np.ndarray:
+    """The layer-1 B operand of the wire kernels for decoded W64 rows ``Xd`` (canonical order,
+    V-columns bf16-exact): [n, 32] float32, bf16-exact."""
+    xin = np.ones((Xd.shape[0], KPAD), np.float32)
+    xin[:, :WIRE_N_BF16] = Xd[:, WIRE_PERM[:WIRE_N_BF16]]
+    t = Xd[:, TIME_COL].astype(np.float32)
+    a = Xd[:, AMOUNT_COL].astype(np.float32)
+    if norm.log_amount:
+        a = np.log1p(np.maximum(a, 0.0)).astype(np.float32)
+    mu, isg = norm.mu, norm.inv_sigma
+    xin[:, WIRE_N_BF16] = (t - mu[TIME_COL]) * isg[TIME_COL]
+    xin[:, WIRE_N_BF16 + 1] = (a - mu[AMOUNT_COL]) * isg[AMOUNT_COL]
+    return bf16_round(xin)
+
+
 @dataclass
 class MLPModel:
     W1: np.ndarray   # [128, 30]
@@ -134,33 +167,12 @@ class MLPModel:
     def _wire_w1(self):
         """Layer-1 matrix of a wire blob [128, 32] (wire K order; V-normalisation and the
         bias hi/lo pair folded in), as float32 before bf16 rounding."""
-        W1p = np.zeros((H1, KPAD), np.float32)
-        W1w = self.W1[:, WIRE_PERM].astype(np.float64)
-        mu = self.norm.mu[WIRE_PERM].astype(np.float64)
-        isg = self.norm.inv_sigma[WIRE_PERM].astype(np.float64)
-        v = np.arange(N_FEATURES) < WIRE_N_BF16
-        W1w[:, v] *= isg[v]
-        b1w = self.b1.astype(np.float64) - W1w[:, v] @ mu[v]
-        W1p[:, :N_FEATURES] = W1w
-        hi = bf16_round(b1w.astype(np.float32))
-        W1p[:, N_FEATURES] = hi
-        W1p[:, N_FEATURES + 1] = bf16_round((b1w - hi).astype(np.float32))
-        return W1p
+        return wire_layer1(self.W1, self.b1, self.norm)
 
     def wire_inputs(self, X: np.ndarray) -> np.ndarray:
         """The layer-1 B operand of the wire kernel, [n, 32] float32 (bf16-exact): raw bf16
         V-columns, bf16 of the normalised Time / Amount, then the two constant-1 bias inputs."""
-        Xd = decode_wire(encode_wire(np.asarray(X, np.float32)))
-        xin = np.ones((Xd.shape[0], KPAD), np.float32)
-        xin[:, :WIRE_N_BF16] = Xd[:, WIRE_PERM[:WIRE_N_BF16]]
-        t = Xd[:, TIME_COL].astype(np.float32)
-        a = Xd[:, AMOUNT_COL].astype(np.float32)
-        if self.norm.log_amount:
-            a = np.log1p(np.maximum(a, 0.0)).astype(np.float32)
-        mu, isg = self.norm.mu, self.norm.inv_sigma
-        xin[:, WIRE_N_BF16] = (t - mu[TIME_COL]) * isg[TIME_COL]
-        xin[:, WIRE_N_BF16 + 1] = (a - mu[AMOUNT_COL]) * isg[AMOUNT_COL]
-        return bf16_round(xin)
+        return wire_operands(self.norm, decode_wire(encode_wire(np.asarray(X, np.float32))))
 
     def wire_logits(self, X: np.ndarray) -> np.ndarray:
         """Numerics oracle of the W64 wire kernel (bf16 operands, fp32/fp64 accumulation)."""

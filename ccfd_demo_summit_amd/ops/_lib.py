@@ -111,6 +111,16 @@ class DriftWireArgs(C.Structure):        # ccfd_drift_wire_args
                 ("n", C.c_int64), ("max_workgroups", C.c_int32), ("pad", C.c_int32)]
 
 
+OUT_BLOB_BYTES, OUTLIER_SLOTS, OUT_FLAG_THRESHOLD = 21312, 66, 1      # ccfd_abi.h CCFD_OUT_*
+
+
+class OutlierArgs(C.Structure):          # ccfd_outlier_args
+    _fields_ = [("rows", C.c_void_p), ("blob", C.c_void_p), ("score", C.c_void_p), ("resid_out", C.c_void_p),
+                ("counts", C.c_void_p), ("n", C.c_int64), ("blob_bytes", C.c_int64), ("latent", C.c_int32),
+                ("magic", C.c_int32), ("max_workgroups", C.c_int32), ("flags", C.c_int32), ("threshold", C.c_float),
+                ("pad", C.c_int32)]
+
+
 class EngineConfig(C.Structure):
     _fields_ = [("device", C.c_int32), ("model", C.c_int32), ("blob", C.c_void_p),
                 ("gbdt_trees", C.c_int32), ("gbdt_depth", C.c_int32), ("threshold", C.c_float),
@@ -198,6 +208,8 @@ def lib() -> C.CDLL:
         L.ccfd_drift_hist_launch.restype = C.c_int
         L.ccfd_drift_wire_launch.argtypes = [C.POINTER(DriftWireArgs), C.c_void_p]
         L.ccfd_drift_wire_launch.restype = C.c_int
+        L.ccfd_outlier_ae_launch.argtypes = [C.POINTER(OutlierArgs), C.c_void_p]
+        L.ccfd_outlier_ae_launch.restype = C.c_int
         L.ccfd_forest_blob_changed.argtypes = [C.c_void_p]
         L.ccfd_forest_blob_changed.restype = None
         L.ccfd_host_alloc.argtypes = [C.c_size_t]

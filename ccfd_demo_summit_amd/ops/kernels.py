@@ -15,7 +15,8 @@ import torch
 
 from ._lib import (ARG_WIRE_G20, ARG_WIRE_G32, ARG_WIRE_W64, BIN_FORMATS, DRIFT_CELLS, DRIFT_COLS, DRIFT_WIRE_EDGES,
                    GBDT_MAX_SPLITS, MODEL_IDS, N_COUNTER_SLOTS, DriftHistArgs, DriftWireArgs, ForestExplainArgs,
-                   GbdtExplainArgs, GbdtHistArgs, GbdtUpdateArgs, MlpExplainArgs, ScoreArgs, ShadowArgs, check, lib)
+                   GbdtExplainArgs, GbdtHistArgs, GbdtUpdateArgs, MlpExplainArgs, OUT_BLOB_BYTES, OUT_FLAG_THRESHOLD,
+                   OUTLIER_SLOTS, OutlierArgs, ScoreArgs, ShadowArgs, check, lib)
 
 N_FEATURES = 30
 ROW_BYTES = {"f32": 4 * N_FEATURES, "w64": 64, "g32": 32, "g20": 20}
@@ -684,6 +685,161 @@ class DriftMonitor:
                     self.tail.view(torch.int64).zero_()
                     torch.cuda.current_stream(self.device).synchronize()
         return DriftReport.compare(self.reference, counts, tail, self.bands, self.min_rows)
+
+    def close(self) -> None:
+        with self._lock:
+            self._stream.synchronize()
+            for p in self._stage:
+                p.free()
+            self._stage = []
+
+
+# ---------------------------------------------------------------------------- outlier scores
+OUTLIER_MAX_WORKGROUPS = 1024       # the launches' default grid bound (4 waves, 128 rows a workgroup and stride)
+
+
+class DeviceOutlierModel:
+    """A ``models.outlier.OutlierAE`` packed (``'AEW1'`` blob) and resident in HBM."""
+
+    def __init__(self, model, device: torch.device | str | int = "cuda"):
+        if getattr(model, "kind", None) != "ae":
+            raise ValueError(f"the outlier kernel takes an OutlierAE (kind 'ae'), not kind {getattr(model, 'kind', None)!r}")
+        self.device = torch.device(device) if not isinstance(device, int) else torch.device("cuda", device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        packed = model.pack()
+        self.latent = int(model.latent)
+        self.threshold = float(model.threshold)
+        self.magic = int(np.frombuffer(packed, np.int32, 1)[0])
+        self.blob = torch.from_numpy(np.frombuffer(packed, np.uint8).copy()).to(self.device)
+        torch.cuda.current_stream(self.device).synchronize()      # usable from any stream from here on
+
+
+def new_outlier_counts(device="cuda") -> torch.Tensor:
+    """Zeroed ``counts uint64 [66]`` for ``outlier_scores`` (slots: ``models.outlier.SLOT_*``)."""
+    return torch.zeros(OUTLIER_SLOTS, dtype=torch.int64, device=device).view(torch.uint64)
+
+
+def _outlier_launch(dev_model: DeviceOutlierModel, ptr: int, n: int, score_ptr: int, resid_ptr: Optional[int],
+                    counts_ptr: Optional[int], threshold: Optional[float], max_workgroups: int,
+                    stream: torch.cuda.Stream) -> None:
+    a = OutlierArgs()
+    a.rows, a.blob, a.score, a.resid_out, a.counts = ptr, dev_model.blob.data_ptr(), score_ptr, resid_ptr, counts_ptr
+    a.n, a.blob_bytes, a.latent, a.magic = int(n), dev_model.blob.numel(), dev_model.latent, dev_model.magic
+    a.max_workgroups = int(max_workgroups)
+    if threshold is not None:
+        a.flags, a.threshold = OUT_FLAG_THRESHOLD, float(threshold)
+    check(lib().ccfd_outlier_ae_launch(C.byref(a), C.c_void_p(stream.cuda_stream)), "ccfd_outlier_ae_launch")
+
+
+def outlier_scores(dev_model: DeviceOutlierModel, rows: torch.Tensor, out: Optional[torch.Tensor] = None,
+                   resid_out: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None,
+                   threshold: Optional[float] = None, max_workgroups: int = OUTLIER_MAX_WORKGROUPS,
+                   stream: Optional[torch.cuda.Stream] = None) -> torch.Tensor:
+    """Autoencoder reconstruction-error scores of W64 rows (csrc/kernels/outlier_ae.hip; oracle
+    ``models.outlier.OutlierAE.wire_scores``).  ``rows``: contiguous CUDA uint8 ``[n,64]``.  Returns
+    ``out``: float32 ``[n]`` (allocated when missing).  ``resid_out``: optional float32 ``[n,32]``, the
+    residuals in wire order (positions 30 / 31 are 0).  ``counts``: optional uint64 ``[66]``
+    (``new_outlier_counts``), ACCUMULATED into: rows, rows with ``score > threshold``, rows with a
+    non-finite score, the 32 ``score_cell`` cells of the finite scores and, for every flagged row,
+    the feature of its largest squared residual.  ``threshold``: ``None`` is the model's.  A row
+    with a non-finite feature scores NaN.  Integer counts: exact and the same for every
+    ``max_workgroups`` (the upper bound on the grid); a row's score does not depend on the batch
+    around it.  ``n == 0`` launches nothing; rows off a 16-byte boundary are refused by the library."""
+    if not isinstance(dev_model, DeviceOutlierModel):
+        raise ValueError("dev_model must be a DeviceOutlierModel")
+    if not rows.is_cuda or rows.dtype != torch.uint8 or rows.dim() != 2 or rows.shape[1] != ROW_BYTES["w64"] or \
+            not rows.is_contiguous():
+        raise ValueError("rows must be contiguous CUDA W64 rows ([n,64] u8)")
+    if rows.device != dev_model.device:
+        raise ValueError("rows must be on the outlier model's device")
+    n = rows.shape[0]
+    if out is None:
+        out = torch.empty(n, dtype=torch.float32, device=rows.device)
+    for name, t, dtype, shape in (("out", out, torch.float32, (n,)), ("resid_out", resid_out, torch.float32, (n, 32)),
+                                  ("counts", counts, torch.uint64, (OUTLIER_SLOTS,))):
+        if t is None:
+            continue
+        if not t.is_cuda or t.device != rows.device or t.dtype != dtype or tuple(t.shape) != shape or \
+                not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous CUDA {str(dtype).split('.')[-1]} tensor of shape "
+                             f"{list(shape)} on the rows' device")
+    s = stream if stream is not None else torch.cuda.current_stream(rows.device)
+    _outlier_launch(dev_model, rows.data_ptr(), n, out.data_ptr(), resid_out.data_ptr() if resid_out is not None else None,
+                    counts.data_ptr() if counts is not None else None, threshold, max_workgroups, s)
+    return out
+
+
+class OutlierMonitor:
+    """A tumbling window of outlier counts of W64 rows on the GPU, built like ``DriftMonitor``.
+
+    ``observe(rows)`` scores CUDA rows on the caller's current stream; ``observe_host(rows)`` copies
+    a host ``uint8 [k,64]`` view into one of two pinned staging buffers and scores it from there on
+    the monitor's own stream (the kernel reads the pinned memory directly), so the caller's memory
+    is free again when it returns.  No score travels to the host: the kernel writes them to a
+    device scratch buffer and only the counts come back, at ``report()`` time.  Thread-safe (one lock)."""
+
+    def __init__(self, model, device: torch.device | str | int = "cuda", max_workgroups: Optional[int] = None):
+        from ..engine.stream_engine import PinnedArray
+        self.model = model
+        self.dev_model = model if isinstance(model, DeviceOutlierModel) else DeviceOutlierModel(model, device)
+        self.device = self.dev_model.device
+        self.threshold = self.dev_model.threshold
+        self.row_bytes = ROW_BYTES["w64"]
+        self.max_workgroups = int(OUTLIER_MAX_WORKGROUPS if max_workgroups is None else max_workgroups)
+        self.counts = new_outlier_counts(self.device)
+        with torch.cuda.device(self.device):
+            self._stream = torch.cuda.Stream(self.device)
+            self._stage = [PinnedArray((DRIFT_STAGE_ROWS, self.row_bytes), np.uint8) for _ in range(2)]
+            self._stage_ptr = [int(lib().ccfd_host_device_ptr(C.c_void_p(p.ptr))) for p in self._stage]
+            self._scratch = torch.empty(DRIFT_STAGE_ROWS, dtype=torch.float32, device=self.device)   # own stream only
+        self._busy: list = [None, None]          # event of the last launch that read each buffer
+        self._next = 0
+        self._streams = {}                       # streams observe() launched on since the last report
+        self._lock = threading.Lock()
+        torch.cuda.current_stream(self.device).synchronize()     # the zeroed counts, before any side-stream launch
+
+    def observe(self, rows: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Score CUDA rows on the current stream and count them; returns the scores."""
+        with self._lock:
+            s = torch.cuda.current_stream(self.device)
+            out = outlier_scores(self.dev_model, rows, out, None, self.counts, None, self.max_workgroups, s)
+            self._streams[s.cuda_stream] = s
+        return out
+
+    def observe_host(self, rows: np.ndarray) -> None:
+        rows = np.asarray(rows)
+        if rows.dtype != np.uint8 or rows.ndim != 2 or rows.shape[1] != self.row_bytes:
+            raise ValueError("rows must be a host uint8 [k,64] array of W64 rows")
+        with self._lock, torch.cuda.device(self.device):     # torch's current device is per thread
+            for lo in range(0, rows.shape[0], DRIFT_STAGE_ROWS):
+                chunk = rows[lo:lo + DRIFT_STAGE_ROWS]
+                b = self._next
+                self._next ^= 1
+                if self._busy[b] is not None:
+                    self._busy[b].synchronize()          # the launch that read this buffer last
+                k = chunk.shape[0]
+                self._stage[b].array[:k] = chunk
+                _outlier_launch(self.dev_model, self._stage_ptr[b], k, self._scratch.data_ptr(), None,
+                                self.counts.data_ptr(), None, self.max_workgroups, self._stream)
+                ev = torch.cuda.Event()
+                ev.record(self._stream)
+                self._busy[b] = ev
+
+    def report(self, reset: bool = False):
+        """``models.outlier.OutlierReport`` of the window so far; ``reset=True`` starts the next one."""
+        from ..models.outlier import OutlierReport
+        with self._lock:
+            self._stream.synchronize()
+            for s in self._streams.values():
+                s.synchronize()
+            self._streams.clear()
+            with torch.cuda.device(self.device):
+                counts = self.counts.view(torch.int64).cpu().numpy().view(np.uint64)
+                if reset:
+                    self.counts.view(torch.int64).zero_()
+                    torch.cuda.current_stream(self.device).synchronize()
+        return OutlierReport.from_counts(counts, self.threshold)
 
     def close(self) -> None:
         with self._lock:

@@ -12,6 +12,10 @@ Shapley attributions of docs/EXPLAIN.md: exact for the trees and LR, sampled for
 window -- binned against the model's table for an oblivious GBDT with a binned reference, as W64
 rows against the reference's own quantile table for an MLP / LR with a W64 reference; any other
 pairing raises ``ValueError`` -- and ``drift()`` reports it (docs/DRIFT.md).
+``set_outlier(model)`` sets a ``models.outlier.OutlierAE`` beside the fraud model: ``outlier(X)`` returns
+``(scores float32 [n], is_outlier bool [n], sq_err float32 [n,30])`` of the rows as W64, every later
+``score(X)`` batch is also counted into an outlier window, and ``outlier_report()`` reports it
+(docs/OUTLIER.md).  The fraud scores do not change.
 """
 from __future__ import annotations
 
@@ -32,10 +36,13 @@ class CpuScorer:
         self._drift = None           # (reference, bins or None for W64, counts, tail) after set_drift
         self._drift_min_rows = 10_000
         self._drift_lock = threading.Lock()
+        self._outlier = None         # (OutlierAE, counts uint64 [66]) after set_outlier
 
     def score(self, X: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
         X = np.asarray(X, np.float32)
         p = self.model.predict_proba(X).astype(np.float32)
+        if self._outlier is not None:
+            self.outlier(X.reshape(-1, X.shape[-1]))
         if self._drift is not None:
             from ..models.drift import bin_counts, wire_bin_counts
             with self._drift_lock:
@@ -70,6 +77,38 @@ class CpuScorer:
                 tail[:] = 0
         return rep
 
+    def set_outlier(self, model) -> None:
+        """Score every later batch with the numpy wire oracle of ``model`` too (``None`` turns it off)."""
+        with self._drift_lock:
+            self._outlier = None if model is None else (_outlier_model(model), np.zeros(_OUT_SLOTS, np.uint64))
+
+    def outlier(self, X: np.ndarray, count: bool = True):
+        """``(scores [n], is_outlier [n], sq_err [n,30] canonical)`` of ``OutlierAE.wire_sq_err``."""
+        from ..models.outlier import recount
+        with self._drift_lock:
+            if self._outlier is None:
+                raise ValueError("no outlier model set (set_outlier)")
+            model, counts = self._outlier
+            rows = encode_wire(np.asarray(X, np.float32).reshape(-1, 30))
+            res = model.wire_residuals(rows)
+            score, sq = model.wire_sq_err(rows)
+            if count:
+                counts += recount(score, res, model.threshold)
+            with np.errstate(invalid="ignore"):
+                return score, score > np.float32(model.threshold), sq
+
+    def outlier_report(self, reset: bool = False):
+        """``models.outlier.OutlierReport`` of the rows seen since ``set_outlier`` / the last reset."""
+        from ..models.outlier import OutlierReport
+        with self._drift_lock:
+            if self._outlier is None:
+                raise ValueError("no outlier model set (set_outlier)")
+            model, counts = self._outlier
+            rep = OutlierReport.from_counts(counts.copy(), model.threshold)
+            if reset:
+                counts[:] = 0
+        return rep
+
     def explain(self, X: np.ndarray) -> Tuple[np.ndarray, float]:
         _explainable(self.model)
         if self.model.kind == "mlp":
@@ -86,6 +125,13 @@ class CpuScorer:
 
 
 EXPLAIN_PERMS, EXPLAIN_SEED = 64, 0      # the MLP's sampled permutations (docs/EXPLAIN.md)
+_OUT_SLOTS = 66                          # models.outlier.OUTLIER_SLOTS
+
+
+def _outlier_model(model):
+    if getattr(model, "kind", None) != "ae":
+        raise ValueError(f"the outlier detector is an OutlierAE (kind 'ae'), not kind {getattr(model, 'kind', None)!r}")
+    return model
 
 
 def _explainable(model) -> None:
@@ -137,6 +183,7 @@ class GpuScorer:
         self._device_index = device_index
         self._explainer = None
         self._drift = None           # (DriftMonitor, bins or None for W64) after set_drift
+        self._outlier = None         # (OutlierAE, OutlierMonitor) after set_outlier
         self.dm = DeviceModel(model, torch.device("cuda", device_index))
         self.engine = StreamEngine(self.dm, batch=max_batch, depth=depth, streams=1,
                                    input_mode="dma", output_mode="zerocopy", threshold=threshold,
@@ -152,7 +199,50 @@ class GpuScorer:
                 rows = X.reshape(-1, X.shape[-1])
                 rows = np.ascontiguousarray(encode_wire(rows) if bins is None else bins.encode(rows))
                 mon.observe(torch.from_numpy(rows).to(mon.device))
+            if self._outlier is not None:
+                import torch
+                mon = self._outlier[1]
+                rows = np.asarray(X, np.float32)
+                mon.observe(torch.from_numpy(encode_wire(rows.reshape(-1, rows.shape[-1]))).to(mon.device))
             return self.engine.score(X)
+
+    def set_outlier(self, model) -> None:
+        """Score every later ``score`` batch with csrc/kernels/outlier_ae.hip too, into an outlier
+        window, and serve ``outlier(X)`` (``None`` turns it off).  The fraud scores do not change."""
+        with self._lock:
+            if self._outlier is not None:
+                self._outlier[1].close()
+                self._outlier = None
+            if model is None:
+                return
+            import torch
+            from ..ops.kernels import OutlierMonitor
+            self._outlier = (_outlier_model(model), OutlierMonitor(model, torch.device("cuda", self._device_index)))
+
+    def outlier(self, X: np.ndarray, count: bool = True):
+        """``(scores float32 [n], is_outlier bool [n], sq_err float32 [n,30] canonical)`` of the rows
+        as W64, from ``ops.kernels.outlier_scores``; ``count`` adds them to the window."""
+        import torch
+        from ..contracts.transaction import WIRE_PERM
+        from ..ops.kernels import outlier_scores
+        with self._lock:
+            if self._outlier is None:
+                raise ValueError("no outlier model set (set_outlier)")
+            model, mon = self._outlier
+            rows = torch.from_numpy(encode_wire(np.asarray(X, np.float32).reshape(-1, 30))).to(mon.device)
+            resid = torch.empty((rows.shape[0], 32), dtype=torch.float32, device=mon.device)
+            score = outlier_scores(mon.dev_model, rows, None, resid, mon.counts if count else None)
+            score, resid = score.cpu().numpy(), resid.cpu().numpy()
+        sq = np.empty((score.shape[0], 30), np.float32)
+        with np.errstate(over="ignore", invalid="ignore"):
+            sq[:, WIRE_PERM] = resid[:, :30] * resid[:, :30]
+            return score, score > np.float32(model.threshold), sq
+
+    def outlier_report(self, reset: bool = False):
+        with self._lock:
+            if self._outlier is None:
+                raise ValueError("no outlier model set (set_outlier)")
+            return self._outlier[1].report(reset=reset)
 
     def set_drift(self, reference, min_rows: int = 10_000) -> None:
         """Count every later ``score`` batch against ``reference`` with
@@ -193,10 +283,13 @@ class GpuScorer:
 
     def close(self):
         self.set_drift(None)
+        self.set_outlier(None)
         self.engine.close()
 
 
 def make_scorer(model, threshold: float = 0.5, device: str = "auto", **kw):
+    if getattr(model, "kind", None) == "ae":
+        raise ValueError("an outlier autoencoder (kind 'ae') is no fraud scorer: set it beside one with set_outlier")
     if device in ("auto", "gpu"):
         try:
             import torch

@@ -14,6 +14,11 @@ Endpoints (port 8000 like ``SELDON_URL=http://modelfull-modelfull:8000``, router
                                PSI per feature of the rows predicted so far against the drift
                                reference (docs/DRIFT.md); POST {"reset": true} starts the next
                                window; 400 without a reference
+  POST /api/v0.1/outlier, /api/v1.0/outlier, /outlier
+                               autoencoder outlier score, flag and worst features of every row of
+                               the same request body (docs/OUTLIER.md); GET: the window's report;
+                               POST {"reset": true} without rows starts the next window; 400
+                               without a detector (``scorer.set_outlier``)
   GET  /prometheus, /metrics   model gauges + seldon_api_engine_* histograms
   GET  /health/ping, /health/status, /ready, /live
 
@@ -123,6 +128,9 @@ class SeldonServer:
         for path in ("/api/v0.1/drift", "/api/v1.0/drift", "/drift"):
             r.add_get(path, self.drift)
             r.add_post(path, self.drift)
+        for path in ("/api/v0.1/outlier", "/api/v1.0/outlier", "/outlier"):
+            r.add_get(path, self.outlier)
+            r.add_post(path, self.outlier)
         r.add_get("/prometheus", self.prometheus)
         r.add_get("/metrics", self.prometheus)
         for path in ("/health/ping", "/ping", "/live", "/ready", "/health/status"):
@@ -214,6 +222,34 @@ class SeldonServer:
         except (seldon.SeldonError, json.JSONDecodeError, ValueError, KeyError) as e:
             return web.json_response(seldon.error_response(400, str(e)), status=400)
         return web.json_response(rep.to_json())
+
+    async def outlier(self, request: web.Request) -> web.Response:
+        """``POST`` with a Seldon request body: per-row ``score`` / ``is_outlier``, the threshold and
+        the top features by squared error (``seldon.build_outlier_response``).  ``GET``: the
+        ``OutlierReport`` of the rows seen since the window began; ``POST {"reset": true}`` with
+        no rows also starts the next window."""
+        if not self._authorized(request):
+            return web.json_response(seldon.error_response(401, "unauthorized"), status=401)
+        try:
+            body = await self._body(request) if request.method == "POST" else {}
+            fn = getattr(self.scorer, "outlier", None)
+            rep_fn = getattr(self.scorer, "outlier_report", None)
+            if fn is None or rep_fn is None or getattr(self.scorer, "_outlier", None) is None:
+                raise seldon.SeldonError("this model has no outlier detector")
+            loop = asyncio.get_running_loop()
+            window = isinstance(body, dict) and "data" not in body and "reset" in body
+            if request.method == "GET" or window:
+                reset = bool(body.get("reset", False)) if isinstance(body, dict) else False
+                rep = await loop.run_in_executor(None, rep_fn, reset)
+                return web.json_response(rep.to_json())
+            X, _names = seldon.parse_request(body)
+            if X.shape[1] != 30:
+                raise seldon.SeldonError("expected 30 features")
+            score, flag, sq = await loop.run_in_executor(None, fn, X)
+            thr = rep_fn(False).threshold
+        except (seldon.SeldonError, json.JSONDecodeError, ValueError, KeyError) as e:
+            return web.json_response(seldon.error_response(400, str(e)), status=400)
+        return web.json_response(seldon.build_outlier_response(score, flag, sq, thr, self.model_name))
 
     async def prometheus(self, _request: web.Request) -> web.Response:
         return web.Response(body=self.metrics.expose(), headers={"Content-Type": CONTENT_TYPE})

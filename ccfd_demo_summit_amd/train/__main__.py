@@ -82,6 +82,13 @@ def main(argv=None) -> int:
                     help="MLP / LR: store the per-feature median or mean of the training rows as the model's "
                          "baseline (fit_baseline), the row its Shapley explanations start from (docs/EXPLAIN.md); "
                          "off by default")
+    ap.add_argument("--outlier-out", default=None, metavar="AE.safetensors",
+                    help="also train the outlier autoencoder (models/outlier.py; `launch seldon|engine|demo "
+                         "--outlier-model`) on the legitimate rows of the same training split, beside any --model, "
+                         "and fit its threshold on the training rows")
+    ap.add_argument("--outlier-latent", type=int, default=8, help="--outlier-out: latent width, 1..32")
+    ap.add_argument("--outlier-quantile", type=float, default=0.999,
+                    help="--outlier-out: the threshold is this quantile of the training rows' scores")
     ap.add_argument("--metrics-port", type=int, default=0,
                     help="serve the trainer's /metrics (the SparkMetrics dashboard series) on this port "
                          "(+ rank) while training; 0 = off")
@@ -147,6 +154,10 @@ def main(argv=None) -> int:
         raise SystemExit("--bits is for --model gbdt (an MLP / LR reference is for W64 rows: --drift-cells)")
     if not 2 <= a.drift_cells <= 32:
         raise SystemExit("--drift-cells is 2..32")
+    if not 1 <= a.outlier_latent <= 32:
+        raise SystemExit("--outlier-latent is 1..32")
+    if not 0.0 < a.outlier_quantile <= 1.0:
+        raise SystemExit("--outlier-quantile is in (0, 1]")
     if a.explain_baseline and a.model == "gbdt":
         raise SystemExit("--explain-baseline is for --model mlp|lr (a GBDT is explained through its cover)")
     if a.model == "gbdt":
@@ -164,6 +175,11 @@ def main(argv=None) -> int:
         model, info = (train_mlp if a.model == "mlp" else train_logistic)(X[tr], y[tr], cfg)
         if a.explain_baseline:
             model = model.fit_baseline(X[tr], a.explain_baseline)
+    ae = ae_info = None
+    if a.outlier_out:
+        from .trainer import train_autoencoder
+        ae, ae_info = train_autoencoder(X[tr], y[tr], TrainConfig(epochs=a.epochs, batch=a.batch, device=dev,
+                                                                  seed=a.seed), latent=a.outlier_latent)
     if rank == 0:
         metrics = evaluate(model, X[te], y[te]) if n_test and 0 < y[te].sum() < n_test else {}
         save_model(model, a.out, version=a.version)
@@ -178,6 +194,14 @@ def main(argv=None) -> int:
             ref.save(a.drift_reference_out)
             out["drift_reference"] = {"out": a.drift_reference_out, "bits": ref.bits, "stamp": ref.stamp,
                                       "rows": ref.rows}
+        if ae is not None:
+            ae.fit_threshold(X[tr], a.outlier_quantile)
+            save_model(ae, a.outlier_out, version=a.version)
+            if n_test and 0 < y[te].sum() < n_test:
+                from sklearn.metrics import roc_auc_score
+                ae_info["test_roc_auc"] = float(roc_auc_score(y[te], ae.scores(X[te])))
+            out["outlier"] = {"out": a.outlier_out, "latent": ae.latent, "threshold": ae.threshold,
+                              "quantile": a.outlier_quantile, "train": ae_info}
         print(json.dumps(out, default=float), flush=True)
     if world > 1:
         dist.barrier()

@@ -191,6 +191,54 @@ def train_mlp(X: np.ndarray, y: np.ndarray, cfg: TrainConfig = TrainConfig()) ->
     return m, info
 
 
+def train_autoencoder(X: np.ndarray, y: np.ndarray, cfg: TrainConfig = TrainConfig(), latent: int = 8,
+                      holdout: float = 0.1):
+    """The outlier autoencoder 30 -> 64 -> latent -> 64 -> 30 (models/outlier.py): MSE on the
+    normalised features of the legitimate (``y == 0``) rows, AdamW, same device / DDP plumbing as
+    ``train_mlp``.  The last ``holdout`` share of the rows (both classes) is kept out of training;
+    the metrics carry the ROC-AUC of the fp32 score against ``y`` there (NaN when it holds one
+    class only).  Returns ``(OutlierAE, metrics)``; the threshold is left to ``fit_threshold``."""
+    from ..models.outlier import HID, OutlierAE
+    X = np.asarray(X, np.float32)
+    y = np.asarray(y)
+    n_hold = int(len(X) * holdout)
+    Xtr, ytr = (X[:-n_hold], y[:-n_hold]) if n_hold else (X, y)
+    norm = Normalizer.fit(Xtr[ytr == 0])
+    dev = _device(cfg.device)
+    torch.manual_seed(cfg.seed)           # reproducible init
+    rank, world = _ddp_ctx()
+    net = nn.Sequential(nn.Linear(X.shape[1], HID), nn.ReLU(), nn.Linear(HID, latent), nn.ReLU(),
+                        nn.Linear(latent, HID), nn.ReLU(), nn.Linear(HID, X.shape[1])).to(dev)
+    model = net
+    if world > 1:
+        from torch.nn.parallel import DistributedDataParallel as DDP
+        model = DDP(net, device_ids=[dev.index] if dev.type == "cuda" else None)
+    Xt = torch.from_numpy(np.ascontiguousarray(norm(Xtr[ytr == 0]))).to(dev)
+    opt = torch.optim.AdamW(model.parameters(), lr=cfg.lr, weight_decay=cfg.weight_decay)
+    g = torch.Generator(device="cpu").manual_seed(cfg.seed)
+    shard = torch.arange(rank, Xt.shape[0], world)
+    steps, last = 0, float("nan")
+    for _ in range(cfg.epochs):
+        perm = shard[torch.randperm(len(shard), generator=g)].to(dev)
+        for s in range(0, len(perm), cfg.batch):
+            xb = Xt[perm[s:s + cfg.batch]]
+            loss = nn.functional.mse_loss(model(xb), xb)
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            opt.step()
+            steps += 1
+        last = float(loss.detach()) if steps else last
+        if cfg.metrics is not None and steps:
+            cfg.metrics.loss.labels("ae").set(last)
+    p = [t.detach().float().cpu().numpy() for t in net.parameters()]
+    m = OutlierAE(p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], norm)
+    info = {"steps": steps, "final_loss": last, "latent": int(latent), "rows": int(Xt.shape[0]), "holdout_roc_auc": float("nan")}
+    if n_hold and 0 < int(y[-n_hold:].sum()) < n_hold:
+        from sklearn.metrics import roc_auc_score
+        info["holdout_roc_auc"] = float(roc_auc_score(y[-n_hold:], m.scores(X[-n_hold:])))
+    return m, info
+
+
 # ---------------------------------------------------------------------------- GBDT
 def _quantile_borders(X: np.ndarray, n_bins: int) -> np.ndarray:
     qs = np.linspace(0, 1, n_bins + 1)[1:-1]

@@ -346,6 +346,43 @@ typedef struct ccfd_drift_wire_args {
 int ccfd_drift_wire_launch(const ccfd_drift_wire_args* a, void* stream);
 
 // ---------------------------------------------------------------------------
+// Outlier scores of W64 rows: the reconstruction error of an autoencoder 30 -> 64 -> L -> 64 -> 30
+// on the matrix unit (outlier_ae.hip; models/outlier.py holds the definition, the 'AEW1' blob,
+// the numpy oracle wire_residuals / wire_scores and the summation order).  For every row:
+// score[i] = mean squared residual; resid_out[i][p] = residual of wire position p (30, 31: 0);
+// counts += {rows, score > threshold, non-finite score, 32 exponent cells of the finite scores,
+// and for a flagged row the canonical feature of its largest squared residual (lowest wire
+// position on a tie)}.  A row with a non-finite feature scores NaN: invalid, never flagged.
+// resid_out and counts are optional (null).  counts is accumulated, never zeroed by the launch.
+// threshold: used when flags & CCFD_OUT_FLAG_THRESHOLD, else the blob header's.  n == 0 returns
+// without a launch (rows and score may then be null); the grid is min(max_workgroups, ceil(n / 128)) workgroups of 4 waves, each
+// wave striding over pairs of 16-row tiles.
+#define CCFD_OUT_BLOB_BYTES 21312
+#define CCFD_OUT_ROWS 0
+#define CCFD_OUT_FLAGGED 1
+#define CCFD_OUT_INVALID 2
+#define CCFD_OUT_HIST 4              // 32 cells: clamp(((bits >> 23) & 255) - 111, 0, 31)
+#define CCFD_OUT_TOP 36              // 30 cells, canonical feature order
+#define CCFD_OUTLIER_SLOTS 66
+#define CCFD_OUT_FLAG_THRESHOLD 1
+typedef struct ccfd_outlier_args {
+  const uint8_t* rows;          // device-visible [n][64], 16-byte aligned
+  const void* blob;             // device 'AEW1' blob, 16-byte aligned
+  float* score;                 // device-visible [n]
+  float* resid_out;             // device-visible [n][32] wire order, 16-byte aligned, or null
+  unsigned long long* counts;   // device [CCFD_OUTLIER_SLOTS], accumulated, or null
+  int64_t n;
+  int64_t blob_bytes;           // must be CCFD_OUT_BLOB_BYTES
+  int32_t latent;               // the blob's L (1..32) and its first word ('AEW1') as the caller read
+  int32_t magic;                // them from the blob it uploaded: the launch checks these copies
+  int32_t max_workgroups;       // upper bound on the grid
+  int32_t flags;
+  float threshold;
+  int32_t pad;
+} ccfd_outlier_args;   // 80 bytes
+int ccfd_outlier_ae_launch(const ccfd_outlier_args* a, void* stream);
+
+// ---------------------------------------------------------------------------
 // Persistent streaming kernel (exec_mode = 1): ONE long-running launch per engine; the
 // host publishes micro-batch descriptors into a ring in coherent pinned memory and bumps
 // `posted`; resident workgroups claim 64..256-row work items with one device atomic, wait for
